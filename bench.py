@@ -10,6 +10,12 @@ timed region is K hipGraph-replayed decode steps (full forward incl.
 lm_head + sampling).
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--model M]
+                       [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints one JSON
+result line; ``--dump-outputs DIR`` additionally saves the last step's
+logits and the emitted token ids as .npy (its untimed prefill skips the
+atomic split-K GEMM path so that the dump is bitwise reproducible at
+batch 1), and ``--full`` is where any secondary measurement belongs.
 Launched by the driver for N>1 via torch.distributed.run (one rank/GPU).
 """
 
@@ -20,6 +26,53 @@ import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+
+DUMP_MAX_BYTES = 24 << 20  # per array; two arrays stay far below 64 MB
+
+
+def emitted_counts(model, batch):
+    """Ids emitted so far, read from the device counters: (B,) int array
+    batched, (1,) at batch 1."""
+    c = model.bt_nout[:batch] if batch > 1 else model.nout
+    return c.cpu().numpy().astype(int)
+
+
+def dump_outputs(out_dir, model, batch, start):
+    """Write the last timed step's results as ``out_dir/<name>.npy``.
+
+    ``start`` is emitted_counts() taken right before the timed region;
+    everything the device appended to the output ring since then is what
+    the timed steps emitted (so a timed loop that ran another number of
+    steps than --steps shows in the array's length).
+
+    ``logits``    float32 — the logits the last step sampled from
+                  ((vocab,) at batch 1, (B, vocab) batched);
+    ``token_ids`` float64 — the ids the timed steps emitted, oldest
+                  first ((steps,) at batch 1, (B, steps) batched).
+    An array above DUMP_MAX_BYTES is reduced to a fixed, seeded sample
+    of its flattened elements (same indices every run).
+    """
+    import numpy as np
+
+    end = emitted_counts(model, batch)
+    if batch > 1:
+        logits = model.bt_logits[:batch].float().cpu().numpy()
+        ring = model.bt_ring[:batch].cpu().numpy()
+        ids = np.stack([ring[b, start[b]:end[b]] for b in range(batch)])
+    else:
+        logits = model.b_logits.float().cpu().numpy()
+        ids = model.out_ring[start[0]:end[0]].cpu().numpy()
+    arrays = {"logits": logits.astype(np.float32),
+              "token_ids": ids.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if a.nbytes > DUMP_MAX_BYTES:
+            keep = DUMP_MAX_BYTES // a.itemsize
+            idx = np.sort(np.random.default_rng(0).choice(
+                a.size, size=keep, replace=False))
+            a = a.ravel()[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def main():
@@ -46,6 +99,17 @@ def main():
                     help="lockstep batched decode (throughput mode; "
                          "value = aggregate tokens/s over the batch)")
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed "
+                         "step computed (logits, sampled token ids) as "
+                         "DIR/<name>.npy; inputs are seeded, so two builds "
+                         "can be compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement or check; "
+                         "a plain run only sets up, warms up, times the "
+                         "steps and prints the result line (there are no "
+                         "secondary measurements yet: the per-kernel, "
+                         "prefill and server figures live in tools/)")
     args = ap.parse_args()
 
     import numpy as np
@@ -89,16 +153,27 @@ def main():
 
     # prefill + warmup
     use_graph = not args.no_graph
+    # The small-M prefill GEMMs split K and accumulate with fp32 atomics,
+    # so the KV they leave differs in the last bits from run to run, and a
+    # greedy rollout over random weights amplifies that into different
+    # tokens.  For a dump that two builds can compare, the (untimed)
+    # prefill runs without the split-K scratch; the decode steps — the
+    # timed path — are exactly those of a plain run.
+    gemm_acc = model.b_gemm_acc
+    if args.dump_outputs:
+        model.b_gemm_acc = None
     if args.batch > 1:
         prompts = rng.integers(0, cfg.vocab_size,
                                size=(args.batch, args.prompt_len))
         model.prefill_batch(prompts)
+        model.b_gemm_acc = gemm_acc
         model.decode_batch(max(args.warmup, 2), greedy=True,
                            use_graph=use_graph)
         if model._graph_mode is None:
             use_graph = False
     else:
         model.prefill(prompt)
+        model.b_gemm_acc = gemm_acc
         if args.warmup > 0:
             model.decode(args.warmup, greedy=True, use_graph=use_graph,
                          first_from_logits=True)
@@ -114,6 +189,11 @@ def main():
                       f"({type(err).__name__ if err else '?'}: {err}); "
                       f"timing eager launches", file=sys.stderr)
             use_graph = False
+
+    # device-side emitted-id counters before the timed region, so the
+    # dump holds what the timed steps really appended (reads sync; untimed)
+    dump_start = (emitted_counts(model, args.batch)
+                  if args.dump_outputs and rank == 0 else None)
 
     # timed region: exactly K decode steps
     barrier()
@@ -140,6 +220,9 @@ def main():
 
     toks_per_s = args.steps * args.batch / elapsed
     ms_per_step = elapsed / args.steps * 1e3
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, args.batch, dump_start)
 
     if rank == 0:
         out = {
