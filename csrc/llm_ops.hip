@@ -29,6 +29,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.h"
 
@@ -57,6 +58,19 @@
 // fuses the k_embed launch into the first QKV GEMV of the decode step.
 #define STAGE_NORM_EMBED 4
 
+// act(gate)*up, bf16-rounded: the one GLU expression (k_glu, STAGE_GLU
+// and the paired-row GEMV epilogue all produce the same bits)
+DEVINL u16 glu_act(float xx, float u, int act) {
+  float a;
+  if (act == 0) {
+    a = xx / (1.f + __expf(-xx));
+  } else {
+    float c = 0.7978845608028654f * (xx + 0.044715f * xx * xx * xx);
+    a = 0.5f * xx * (1.f + tanhf(c));
+  }
+  return f2b(a * u);
+}
+
 // staging helper shared by bf16/fp8 GEMV (RMSNorm / GLU fused pre-ops)
 DEVINL float stage_red_sum(float* red) {
   const int nw = blockDim.x >> 6;
@@ -65,27 +79,63 @@ DEVINL float stage_red_sum(float* red) {
   return t;
 }
 
-DEVINL const u16* gemv_stage(char* smem, const u16* x, const u16* x2,
-                             const float* g, const float* g2, u16* hout,
-                             int K, int stage, int act, float eps,
+// The bf16 staging pass is split in two so the GEMV can put its first
+// weight loads between them: gemv_stage_issue() issues every global
+// load of the pass's FIRST iteration (i0 = tid*8: all of it for
+// K <= 8*blockDim) into registers, the kernel then issues its weight
+// prologue, and gemv_stage() does the arithmetic, barriers and LDS
+// writes.  vmcnt retires in order, so only loads issued BEFORE the
+// weights can be waited for without draining the weight stream too.
+// Addresses are clamped instead of predicated (unconditional loads; a
+// thread with i0 >= K ignores what it fetched).
+struct StagePre {
+  s8v v, hv;             // x (GLU: gate) / h (GLU: up) chunk
+  f4v ga, gb;            // gamma chunk (fp32)
+};
+
+DEVINL void gemv_stage_issue(StagePre& p, const u16*& x, const u16* x2,
+                             const float* g, int K, int stage) {
+  int i = threadIdx.x * 8;
+  if (i > K - 8) i = K - 8;
+  if (stage == STAGE_NORM_EMBED)  // x = table: gather row *x2 (token id)
+    x += (size_t)(*(const int*)x2) * (size_t)K;
+  p.v = *(const s8v*)(x + i);
+  if (stage == STAGE_NORM2 || stage == STAGE_GLU)
+    p.hv = *(const s8v*)(x2 + i);
+  if (stage == STAGE_NORM || stage == STAGE_NORM_EMBED ||
+      stage == STAGE_NORM2) {
+    p.ga = *(const f4v*)(g + i);
+    p.gb = *(const f4v*)(g + i + 4);
+  }
+  // NORM2's g2 is NOT hoisted: 8 more live VGPRs cost the RPW=1 kernel a
+  // wave of occupancy, and its first use sits behind three barriers, by
+  // when the prologue loads it then waits for have long landed
+}
+
+// x is the pointer gemv_stage_issue left (NORM_EMBED: the gathered row)
+DEVINL const u16* gemv_stage(char* smem, const StagePre& p, const u16* x,
+                             const u16* x2, const float* g, const float* g2,
+                             u16* hout, int K, int stage, int act, float eps,
                              float escale) {
   u16* xs = (u16*)smem;
   const int STRIDE = blockDim.x * 8;
+  const int i0 = threadIdx.x * 8;
+  float* red = (float*)(smem + (size_t)K * 2);
   if (stage == STAGE_NORM2) {
     // x2 = h_in (read-only here); block 0 persists h' into hout — a
     // DIFFERENT buffer (ping-pong), since other blocks still read h_in
     const u16* h = x2;
-    float* red = (float*)(smem + (size_t)K * 2);
     // pass 1: sumsq of x (the un-normed projection output t)
     float ss = 0.f;
-    for (int i = threadIdx.x * 8; i < K; i += STRIDE) {
-      s8v v = *(const s8v*)(x + i);
+    auto p1 = [&](s8v v) {
 #pragma unroll
       for (int j = 0; j < 8; j++) {
         float f = b2f(((u16*)&v)[j]);
         ss += f * f;
       }
-    }
+    };
+    if (i0 < K) p1(p.v);
+    for (int i = i0 + STRIDE; i < K; i += STRIDE) p1(*(const s8v*)(x + i));
     ss = wave_reduce_sum(ss);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
     __syncthreads();
@@ -94,11 +144,7 @@ DEVINL const u16* gemv_stage(char* smem, const u16* x, const u16* x2,
     // pass 2: h' = h + norm_a(x)*g (bf16-rounded, matching the
     // standalone k_rmsnorm mode 1), stash h' in LDS, sumsq of h'
     float ss2 = 0.f;
-    for (int i = threadIdx.x * 8; i < K; i += STRIDE) {
-      s8v v = *(const s8v*)(x + i);
-      s8v hv = *(const s8v*)(h + i);
-      f4v ga = *(const f4v*)(g + i);
-      f4v gb = *(const f4v*)(g + i + 4);
+    auto p2 = [&](int i, s8v v, s8v hv, f4v ga, f4v gb) {
       u16 o[8];
 #pragma unroll
       for (int j = 0; j < 8; j++) {
@@ -110,36 +156,36 @@ DEVINL const u16* gemv_stage(char* smem, const u16* x, const u16* x2,
       }
       *(s8v*)(xs + i) = *(s8v*)o;
       if (blockIdx.x == 0) *(s8v*)(hout + i) = *(s8v*)o;  // persist h'
-    }
+    };
+    if (i0 < K) p2(i0, p.v, p.hv, p.ga, p.gb);
+    for (int i = i0 + STRIDE; i < K; i += STRIDE)
+      p2(i, *(const s8v*)(x + i), *(const s8v*)(h + i),
+         *(const f4v*)(g + i), *(const f4v*)(g + i + 4));
     ss2 = wave_reduce_sum(ss2);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss2;
     __syncthreads();
     float rnorm_b = rsqrtf(stage_red_sum(red) / (float)K + eps);
     // pass 3: xs = norm_b(h')*g2
-    for (int i = threadIdx.x * 8; i < K; i += STRIDE) {
+    auto p3 = [&](int i, f4v ga, f4v gb) {
       s8v v = *(s8v*)(xs + i);
-      f4v ga = *(const f4v*)(g2 + i);
-      f4v gb = *(const f4v*)(g2 + i + 4);
       u16 o[8];
 #pragma unroll
       for (int j = 0; j < 8; j++)
         o[j] = f2b(b2f(((u16*)&v)[j]) * rnorm_b *
                    (j < 4 ? ga[j] : gb[j - 4]));
       *(s8v*)(xs + i) = *(s8v*)o;
-    }
+    };
+    for (int i = i0; i < K; i += STRIDE)
+      p3(i, *(const f4v*)(g2 + i), *(const f4v*)(g2 + i + 4));
     __syncthreads();
     return xs;
   }
   if (stage == STAGE_NORM || stage == STAGE_NORM_EMBED) {
-    // NORM_EMBED: x is the embedding TABLE; gather row *x2 (token id),
-    // scale by escale (bf16-rounded, matching the standalone k_embed),
-    // and have block 0 persist it as the residual-stream h
-    const u16* xsrc = x;
-    if (stage == STAGE_NORM_EMBED)
-      xsrc = x + (size_t)(*(const int*)x2) * (size_t)K;
+    // NORM_EMBED: the gathered row is scaled by escale (bf16-rounded,
+    // matching the standalone k_embed), and block 0 persists it as the
+    // residual-stream h
     float ss = 0.f;
-    for (int i = threadIdx.x * 8; i < K; i += STRIDE) {
-      s8v v = *(const s8v*)(xsrc + i);
+    auto p1 = [&](int i, s8v v) {
       if (stage == STAGE_NORM_EMBED) {
         u16 o[8];
 #pragma unroll
@@ -154,42 +200,40 @@ DEVINL const u16* gemv_stage(char* smem, const u16* x, const u16* x2,
         float f = b2f(((u16*)&v)[j]);
         ss += f * f;
       }
-    }
-    float* red = (float*)(smem + (size_t)K * 2);
+    };
+    if (i0 < K) p1(i0, p.v);
+    for (int i = i0 + STRIDE; i < K; i += STRIDE)
+      p1(i, *(const s8v*)(x + i));
     ss = wave_reduce_sum(ss);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
     __syncthreads();
     float rnorm = rsqrtf(stage_red_sum(red) / (float)K + eps);
-    for (int i = threadIdx.x * 8; i < K; i += STRIDE) {
+    auto p2 = [&](int i, f4v ga, f4v gb) {
       s8v v = *(s8v*)(xs + i);
       u16 o[8];
 #pragma unroll
       for (int j = 0; j < 8; j++)
-        o[j] = f2b(b2f(((u16*)&v)[j]) * rnorm * g[i + j]);
+        o[j] = f2b(b2f(((u16*)&v)[j]) * rnorm *
+                   (j < 4 ? ga[j] : gb[j - 4]));
       *(s8v*)(xs + i) = *(s8v*)o;
-    }
-  } else if (stage == STAGE_GLU) {
-    for (int i = threadIdx.x * 8; i < K; i += STRIDE) {
-      s8v gv = *(const s8v*)(x + i);
-      s8v uv = *(const s8v*)(x2 + i);
+    };
+    if (i0 < K) p2(i0, p.ga, p.gb);
+    for (int i = i0 + STRIDE; i < K; i += STRIDE)
+      p2(i, *(const f4v*)(g + i), *(const f4v*)(g + i + 4));
+  } else {  // STAGE_GLU
+    auto p1 = [&](int i, s8v gv, s8v uv) {
       u16 o[8];
 #pragma unroll
-      for (int j = 0; j < 8; j++) {
-        float xx = b2f(((u16*)&gv)[j]);
-        float a;
-        if (act == 0) {
-          a = xx / (1.f + __expf(-xx));
-        } else {
-          float c = 0.7978845608028654f * (xx + 0.044715f * xx * xx * xx);
-          a = 0.5f * xx * (1.f + tanhf(c));
-        }
-        o[j] = f2b(a * b2f(((u16*)&uv)[j]));
-      }
+      for (int j = 0; j < 8; j++)
+        o[j] = glu_act(b2f(((u16*)&gv)[j]), b2f(((u16*)&uv)[j]), act);
       *(s8v*)(xs + i) = *(s8v*)o;
-    }
+    };
+    if (i0 < K) p1(i0, p.v, p.hv);
+    for (int i = i0 + STRIDE; i < K; i += STRIDE)
+      p1(i, *(const s8v*)(x + i), *(const s8v*)(x2 + i));
   }
-  if (stage != STAGE_RAW) __syncthreads();
-  return (stage == STAGE_RAW) ? x : xs;  // RAW: L2-hot, no barrier
+  __syncthreads();
+  return xs;
 }
 
 // f32 variant of the staging pass, used by the fp8 GEMV: x lands in LDS
@@ -321,62 +365,71 @@ DEVINL void gemv_epilogue(float acc, int row, void* y, const u16* res,
   else ((u16*)y)[row] = f2b(acc);
 }
 
-// NT: non-temporal weight loads (read-once stream, keep L2 for x/KV —
-// MI355X_MICROARCH "nt-weights").  RPW: rows per wave (ILP: RPW x 4
-// weight loads in flight).
-template <bool NT, int RPW>
-__global__ void __launch_bounds__(512)
-k_gemv_bf16_t(const u16* __restrict__ W, const u16* __restrict__ x,
-              const u16* __restrict__ x2, const float* __restrict__ g,
-              const float* __restrict__ g2, void* __restrict__ y,
-              const u16* __restrict__ res, int N, int K, int stage, int act,
-              float eps, int out_f32, float softcap, float escale,
-              const int* __restrict__ eidx, long wstride,
-              const float* __restrict__ oscale) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const u16* xv = gemv_stage(smem, x, x2, g, g2, (u16*)res, K, stage, act,
-                             eps, escale);
-  // MoE: expert-indexed weight base + device output scale (router
-  // prob); scalar loads, uniform branch — free on the dense path
-  if (eidx) W += (size_t)(*eidx) * wstride;
-  const float osc = oscale ? *oscale : 1.0f;
-  // NORM2 / NORM_EMBED borrow `res` as the persisted-h output
-  const u16* eres = (stage == STAGE_NORM2 || stage == STAGE_NORM_EMBED)
-                        ? nullptr : res;
+template <bool NT>
+DEVINL s8v gemv_wload(const u16* p) {
+  return NT ? __builtin_nontemporal_load((const s8v*)p) : *(const s8v*)p;
+}
 
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int wpb = blockDim.x >> 6;
-  const int rstride = gridDim.x * wpb * RPW;  // grid-stride rows
-  for (int row0 = (blockIdx.x * wpb + wave) * RPW; row0 < N;
-       row0 += rstride) {                    // wave setup over many rows
-  const u16* Wr[RPW];
-  float a0[RPW], a1[RPW], a2[RPW], a3[RPW];
+// One grid-stride iteration's dot products: NR rows in flight against
+// the staged vector; acc[r] is the lane's partial sum of row r.
+// PRE: the first four 16 B chunks of each row (pw[r][q], at
+// lane*8 + 512q clamped to K-8) were loaded ahead of the staging pass
+// and stand in for the loads the loops would issue first — the same
+// chunks into the same accumulators in the same order, so the sums are
+// bit-identical with and without the prologue.
+template <bool NT, int NR, bool PRE>
+DEVINL void gemv_rows(const u16* (&Wr)[NR], const u16* xv, int K, int lane,
+                      const s8v (&pw)[NR][4], float (&acc)[NR]) {
+  float a0[NR], a1[NR], a2[NR], a3[NR];
 #pragma unroll
-  for (int r = 0; r < RPW; r++) {
-    int rr = row0 + r < N ? row0 + r : N - 1;
-    Wr[r] = W + (size_t)rr * K;
-    a0[r] = a1[r] = a2[r] = a3[r] = 0.f;
-  }
+  for (int r = 0; r < NR; r++) a0[r] = a1[r] = a2[r] = a3[r] = 0.f;
   int k = lane * 8;
+  if (PRE) {
+    if (k + 1536 < K) {  // the main loop's first iteration
+      s8v x0 = *(const s8v*)(xv + k);
+      s8v x1 = *(const s8v*)(xv + k + 512);
+      s8v x2v = *(const s8v*)(xv + k + 1024);
+      s8v x3 = *(const s8v*)(xv + k + 1536);
+#pragma unroll
+      for (int r = 0; r < NR; r++) {
+        s8v w0 = pw[r][0], w1 = pw[r][1], w2 = pw[r][2], w3 = pw[r][3];
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+          a0[r] += b2f(((u16*)&w0)[j]) * b2f(((u16*)&x0)[j]);
+          a1[r] += b2f(((u16*)&w1)[j]) * b2f(((u16*)&x1)[j]);
+          a2[r] += b2f(((u16*)&w2)[j]) * b2f(((u16*)&x2v)[j]);
+          a3[r] += b2f(((u16*)&w3)[j]) * b2f(((u16*)&x3)[j]);
+        }
+      }
+      k += 2048;
+    } else {  // K too short for it: the tail loop's (at most 3) iterations
+#pragma unroll
+      for (int q = 0; q < 3; q++) {
+        if (k < K) {
+          s8v x0 = *(const s8v*)(xv + k);
+#pragma unroll
+          for (int r = 0; r < NR; r++) {
+            s8v w0 = pw[r][q];
+#pragma unroll
+            for (int j = 0; j < 8; j++)
+              a0[r] += b2f(((u16*)&w0)[j]) * b2f(((u16*)&x0)[j]);
+          }
+          k += 512;
+        }
+      }
+    }
+  }
   for (; k + 1536 < K; k += 2048) {
     s8v x0 = *(const s8v*)(xv + k);
     s8v x1 = *(const s8v*)(xv + k + 512);
     s8v x2v = *(const s8v*)(xv + k + 1024);
     s8v x3 = *(const s8v*)(xv + k + 1536);
 #pragma unroll
-    for (int r = 0; r < RPW; r++) {
-      s8v w0, w1, w2, w3;
-      if (NT) {
-        w0 = __builtin_nontemporal_load((const s8v*)(Wr[r] + k));
-        w1 = __builtin_nontemporal_load((const s8v*)(Wr[r] + k + 512));
-        w2 = __builtin_nontemporal_load((const s8v*)(Wr[r] + k + 1024));
-        w3 = __builtin_nontemporal_load((const s8v*)(Wr[r] + k + 1536));
-      } else {
-        w0 = *(const s8v*)(Wr[r] + k);
-        w1 = *(const s8v*)(Wr[r] + k + 512);
-        w2 = *(const s8v*)(Wr[r] + k + 1024);
-        w3 = *(const s8v*)(Wr[r] + k + 1536);
-      }
+    for (int r = 0; r < NR; r++) {
+      s8v w0 = gemv_wload<NT>(Wr[r] + k);
+      s8v w1 = gemv_wload<NT>(Wr[r] + k + 512);
+      s8v w2 = gemv_wload<NT>(Wr[r] + k + 1024);
+      s8v w3 = gemv_wload<NT>(Wr[r] + k + 1536);
 #pragma unroll
       for (int j = 0; j < 8; j++) {
         a0[r] += b2f(((u16*)&w0)[j]) * b2f(((u16*)&x0)[j]);
@@ -389,23 +442,114 @@ k_gemv_bf16_t(const u16* __restrict__ W, const u16* __restrict__ x,
   for (; k < K; k += 512) {
     s8v x0 = *(const s8v*)(xv + k);
 #pragma unroll
-    for (int r = 0; r < RPW; r++) {
-      s8v w0 = NT ? __builtin_nontemporal_load((const s8v*)(Wr[r] + k))
-                  : *(const s8v*)(Wr[r] + k);
+    for (int r = 0; r < NR; r++) {
+      s8v w0 = gemv_wload<NT>(Wr[r] + k);
 #pragma unroll
       for (int j = 0; j < 8; j++)
         a0[r] += b2f(((u16*)&w0)[j]) * b2f(((u16*)&x0)[j]);
     }
   }
 #pragma unroll
-  for (int r = 0; r < RPW; r++) {
-    float acc = osc * wave_reduce_sum((a0[r] + a1[r]) + (a2[r] + a3[r]));
-    if (lane == 0 && row0 + r < N)
-      gemv_epilogue(acc, row0 + r, y, eres, out_f32, softcap);
-  }
-  }  // row0 grid-stride loop
+  for (int r = 0; r < NR; r++) acc[r] = (a0[r] + a1[r]) + (a2[r] + a3[r]);
 }
 
+// NT: non-temporal weight loads (read-once stream, keep L2 for x/KV —
+// MI355X_MICROARCH "nt-weights").  RPW: rows per wave (ILP: RPW x 4
+// weight loads in flight).
+// PAIR (fused GLU, W = [2N, K] gate rows then up rows, y[N]): the wave
+// that owns output n accumulates gate row n and up row n+N and writes
+// act(gate)*up itself — both sums bf16-rounded first, so the bits equal
+// "GEMV into 2N, then GLU".  The two rows are in flight together (RPW
+// must be 2).
+// Every staged launch (stage != RAW) issues the weight loads of its
+// first row iteration BEFORE the staging pass's barriers (see
+// gemv_stage_issue): the stream's first round trip overlaps the stage's.
+// The second launch bound pins the parent kernel's occupancy (5 waves/
+// SIMD at RPW 1, 4 at RPW 2): the prologue's live registers sit right at
+// those VGPR boundaries, and one wave less leaves a 1024-block grid with
+// a partial last round (measured 1398 -> 1320 tok/s).
+template <bool NT, int RPW, bool PAIR>
+__global__ void __launch_bounds__(512, RPW == 1 ? 5 : 4)
+k_gemv_bf16_t(const u16* __restrict__ W, const u16* __restrict__ x,
+              const u16* __restrict__ x2, const float* __restrict__ g,
+              const float* __restrict__ g2, void* __restrict__ y,
+              const u16* __restrict__ res, int N, int K, int stage, int act,
+              float eps, int out_f32, float softcap, float escale,
+              const int* __restrict__ eidx, long wstride,
+              const float* __restrict__ oscale) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  static_assert(!PAIR || RPW == 2, "PAIR: gate and up row in flight");
+  constexpr int NR = RPW;              // rows in flight
+  constexpr int OPW = PAIR ? 1 : RPW;  // outputs per wave iteration
+  // MoE: expert-indexed weight base + device output scale (router
+  // prob); scalar loads, uniform branch — free on the dense path
+  if (eidx) W += (size_t)(*eidx) * wstride;
+  const float osc = oscale ? *oscale : 1.0f;
+  // NORM2 / NORM_EMBED borrow `res` as the persisted-h output
+  const u16* eres = (stage == STAGE_NORM2 || stage == STAGE_NORM_EMBED)
+                        ? nullptr : res;
+
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int wpb = blockDim.x >> 6;
+  const int rstride = gridDim.x * wpb * OPW;  // grid-stride rows
+  int row0 = (blockIdx.x * wpb + wave) * OPW;
+  // row r of the iteration at `row`: rows row..row+RPW-1, or (PAIR)
+  // gate row `row` / up row `row`+N; clamped so idle waves stay in bounds
+  auto rowptr = [&](int row, int r) {
+    int rr = PAIR ? row : row + r;
+    rr = rr < N ? rr : N - 1;
+    if (PAIR) rr += r * N;
+    return W + (size_t)rr * K;
+  };
+
+  const u16* xv = x;  // RAW: L2-hot, no barrier, nothing to overlap
+  s8v pw[NR][4];
+  if (stage != STAGE_RAW) {
+    StagePre sp;
+    const u16* xsrc = x;
+    gemv_stage_issue(sp, xsrc, x2, g, K, stage);
+#pragma unroll
+    for (int r = 0; r < NR; r++) {
+      const u16* wr = rowptr(row0, r);
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        int kq = lane * 8 + 512 * q;
+        if (kq > K - 8) kq = K - 8;
+        pw[r][q] = gemv_wload<NT>(wr + kq);
+      }
+    }
+    xv = gemv_stage(smem, sp, xsrc, x2, g, g2, (u16*)res, K, stage, act, eps,
+                    escale);
+  }
+
+  auto body = [&](auto pre, int row) {
+    const u16* Wr[NR];
+    float acc[NR];
+#pragma unroll
+    for (int r = 0; r < NR; r++) Wr[r] = rowptr(row, r);
+    gemv_rows<NT, NR, decltype(pre)::value>(Wr, xv, K, lane, pw, acc);
+    if (PAIR) {
+      const float ag = osc * wave_reduce_sum(acc[0]);
+      const float au = osc * wave_reduce_sum(acc[NR - 1]);
+      if (lane == 0 && row < N)
+        ((u16*)y)[row] = glu_act(b2f(f2b(ag)), b2f(f2b(au)), act);
+    } else {
+#pragma unroll
+      for (int r = 0; r < NR; r++) {
+        float a = osc * wave_reduce_sum(acc[r]);
+        if (lane == 0 && row + r < N)
+          gemv_epilogue(a, row + r, y, eres, out_f32, softcap);
+      }
+    }
+  };
+  if (stage != STAGE_RAW && row0 < N) {  // consumes the prologue loads
+    body(std::true_type{}, row0);
+    row0 += rstride;
+  }
+  for (; row0 < N; row0 += rstride) body(std::false_type{}, row0);
+}
+
+// glu_pair: N counts the rows of W ([gate; up]); y gets N/2 outputs
 extern "C" hipError_t launch_gemv_bf16(const void* W, const void* x,
                                        const void* x2, const void* g,
                                        const void* g2, void* y,
@@ -415,34 +559,45 @@ extern "C" hipError_t launch_gemv_bf16(const void* W, const void* x,
                                        int nt, int rpw, int maxblocks,
                                        float escale, const void* eidx,
                                        long wstride, const void* oscale,
-                                       hipStream_t stream) {
+                                       hipStream_t stream, int glu_pair) {
   size_t lds = (stage == STAGE_RAW) ? 0 : ((size_t)K * 2 + 32);
   static int rpw_env_b = -1;
   if (rpw_env_b < 0) {
     const char* p = getenv("LLM_GEMV_RPW");
     rpw_env_b = p ? atoi(p) : 0;
   }
-  if (rpw_env_b > 0) rpw = rpw_env_b;
+  if (glu_pair) {
+    const bool hres = stage == STAGE_NORM2 || stage == STAGE_NORM_EMBED;
+    if ((N & 1) || (res && !hres) || softcap > 0.f || out_f32 || eidx ||
+        oscale || stage == STAGE_GLU)
+      return hipErrorInvalidValue;
+    N /= 2;
+    rpw = 2;  // gate row + up row
+  } else if (rpw_env_b > 0) rpw = rpw_env_b;
   else if (rpw <= 1)
     // deep-K only: the fp8 GEMV's large-N rpw rule measured NEGATIVE
     // for bf16 (1b 1234->1218, gemma-2b 536->526)
     rpw = (K >= 3584 && N >= 3072) ? 2 : 1;
   int threads = 256;  // 512 measured slower (fp8 1391->1328)
   int wpb = threads / 64;
-  int blocks = (N + wpb * rpw - 1) / (wpb * rpw);
+  int opw = glu_pair ? 1 : rpw;  // outputs per wave iteration
+  int blocks = (N + wpb * opw - 1) / (wpb * opw);
   int cap = maxblocks > 0 ? maxblocks : 1024;
   if (blocks > cap) blocks = cap;  // grid-stride the rest (Guideline 11)
-#define GEMV_CASE(NTV, RPWV)                                                 \
-  hipLaunchKernelGGL((k_gemv_bf16_t<NTV, RPWV>), dim3(blocks), dim3(threads),\
+#define GEMV_CASE(NTV, RPWV, PV)                                             \
+  hipLaunchKernelGGL((k_gemv_bf16_t<NTV, RPWV, PV>), dim3(blocks),           \
+                     dim3(threads),                                          \
                      lds, stream, (const u16*)W, (const u16*)x,              \
                      (const u16*)x2, (const float*)g, (const float*)g2, y,   \
                      (const u16*)res, N, K, stage, act, eps, out_f32,        \
                      softcap, escale, (const int*)eidx, wstride,             \
                      (const float*)oscale)
-  if (nt && rpw == 2) GEMV_CASE(true, 2);
-  else if (nt) GEMV_CASE(true, 1);
-  else if (rpw == 2) GEMV_CASE(false, 2);
-  else GEMV_CASE(false, 1);
+  if (glu_pair && nt) GEMV_CASE(true, 2, true);
+  else if (glu_pair) GEMV_CASE(false, 2, true);
+  else if (nt && rpw == 2) GEMV_CASE(true, 2, false);
+  else if (nt) GEMV_CASE(true, 1, false);
+  else if (rpw == 2) GEMV_CASE(false, 2, false);
+  else GEMV_CASE(false, 1, false);
 #undef GEMV_CASE
   return hipGetLastError();
 }

@@ -958,11 +958,21 @@ class GPUModel:
     def _decode_step(self, greedy: bool, min_p: float,
                      temperature: float = 1.0):
         """Fused decode path: 4 kernels/layer (llama) or 5 (gemma) —
-        RMSNorm and GLU live inside the GEMV staging pass, RoPE + KV
-        write inside the attention kernel; a side stream prefetches the
-        next layer's weights through MALL, paced by per-layer events."""
+        RMSNorm lives inside the GEMV staging pass, RoPE + KV write
+        inside the attention kernel.  bf16 weights: the gate+up GEMV
+        computes the GLU itself (paired rows) and the down projection
+        reads the I-long activation directly; fp8 / MXFP4 weights: the
+        GLU is the down projection's staging pre-op.  The side-stream
+        weight prefetcher (`prefetch_on`) is off unless asked for."""
         cfg = self.config
         eps = cfg.rms_norm_eps
+        if self.fp8 or self.wq4:
+            gukw = {}
+            downkw = dict(stage=ho.STAGE_GLU, x2=self.b_gu[self.inter_l:],
+                          act=self.act)
+        else:
+            gukw = dict(glu_pair=True, act=self.act)
+            downkw = {}  # RAW: x straight from L2 per wave, as o_proj
         h = self.b_h[0]
         hnext = self.b_hb
         t1 = self.b_t1[0]
@@ -1016,11 +1026,10 @@ class GPUModel:
                 # stage = norm(h')*g_preffn — both sandwich norms fused
                 self._dgemv(lw, "wgu", t1, self.b_gu, stage=ho.STAGE_NORM2,
                             x2=h, g=lw["g_post"], g2=lw["g_preffn"],
-                            res=hnext, eps=eps)
+                            res=hnext, eps=eps, **gukw)
                 h, hnext = hnext, h
                 self._dgemv(lw, "wdown", self.b_gu[:self.inter_l], t2,
-                            stage=ho.STAGE_GLU, x2=self.b_gu[self.inter_l:],
-                            act=self.act)
+                            **downkw)
                 tpu.all_reduce(t2)
             else:
                 if self.tp_branch:
@@ -1062,17 +1071,15 @@ class GPUModel:
                                     wstride=H * I, oscale=osc)
                     continue
                 self._dgemv(lw, "wgu", h, self.b_gu, stage=ho.STAGE_NORM,
-                            g=lw["g_post"], eps=eps)
+                            g=lw["g_post"], eps=eps, **gukw)
                 if self.tp_branch:
                     self._dgemv(lw, "wdown", self.b_gu[:self.inter_l], t1,
-                                stage=ho.STAGE_GLU,
-                                x2=self.b_gu[self.inter_l:], act=self.act)
+                                **downkw)
                     tpu.all_reduce(t1)
                     ho.addinto(h, t1)
                 else:
                     self._dgemv(lw, "wdown", self.b_gu[:self.inter_l], h,
-                                res=h, stage=ho.STAGE_GLU,
-                                x2=self.b_gu[self.inter_l:], act=self.act)
+                                res=h, **downkw)
         if pf:
             ev = torch.cuda.Event()
             ev.record(self._pf_stream)

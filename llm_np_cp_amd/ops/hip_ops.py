@@ -28,7 +28,7 @@ _SIGS = {
                         [ctypes.c_float, ctypes.c_int, ctypes.c_float,
                          ctypes.c_int, ctypes.c_int, ctypes.c_int,
                          ctypes.c_float, ctypes.c_void_p, ctypes.c_long,
-                         ctypes.c_void_p, ctypes.c_void_p],
+                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int],
     "launch_gemv_fp8": [ctypes.c_void_p] * 8 + [ctypes.c_int] * 4 +
                        [ctypes.c_float, ctypes.c_int, ctypes.c_float,
                         ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -170,20 +170,39 @@ def gemv(W: torch.Tensor, x: torch.Tensor, y: torch.Tensor,
          nt: int = 1, rpw: int = 1, maxblocks: int = 0,
          g2: torch.Tensor | None = None, escale: float = 1.0,
          eidx: torch.Tensor | None = None, wstride: int = 0,
-         oscale: torch.Tensor | None = None):
+         oscale: torch.Tensor | None = None, glu_pair: bool = False):
     """y[N] = W[N,K] @ stage(x)[K] (+res); stage fuses RMSNorm / GLU /
     the Gemma sandwich (NORM2: x2 = h_in, g/g2 = post/pre gammas, res =
     h_out ping-pong) / the embed gather (NORM_EMBED: x = embed table,
     x2 = token-id i32, res = persisted h) into the LDS staging pass;
-    nt = non-temporal W."""
+    nt = non-temporal W.
+
+    glu_pair: W = [gate rows; up rows] ([2I, K]) and y[I] =
+    act(W[n] @ xs) * (W[n+I] @ xs), both sums bf16-rounded first — the
+    bits of "gemv into 2I, then glu", in one launch.  Composes with the
+    input stages only: no res / softcap / fp32 output / MoE indexing."""
     N, K = W.shape
     out_f32 = 1 if y.dtype == torch.float32 else 0
+    if glu_pair:
+        hres = stage in (STAGE_NORM2, STAGE_NORM_EMBED)  # res = h out
+        bad = [n for n, on in (("res", res is not None and not hres),
+                               ("softcap", softcap > 0.0),
+                               ("fp32 output", bool(out_f32)),
+                               ("eidx", eidx is not None),
+                               ("oscale", oscale is not None),
+                               ("stage=GLU", stage == STAGE_GLU)) if on]
+        if bad:
+            raise ValueError("gemv(glu_pair=True) does not compose with "
+                             + ", ".join(bad))
+        if N % 2 or y.numel() < N // 2:
+            raise ValueError(f"gemv(glu_pair=True): W has {N} rows, y "
+                             f"{y.numel()} elements; need y >= rows/2")
     _check(lib().launch_gemv_bf16(
         _ptr(W), _ptr(x), _ptr(x2), _ptr(g), _ptr(g2), _ptr(y), _ptr(res),
         N, K, stage, act, ctypes.c_float(eps), out_f32,
         ctypes.c_float(softcap), nt, rpw, maxblocks,
         ctypes.c_float(escale), _ptr(eidx), ctypes.c_long(wstride),
-        _ptr(oscale), _stream()), "gemv")
+        _ptr(oscale), _stream(), 1 if glu_pair else 0), "gemv")
 
 
 def gemv_fp8(Wq: torch.Tensor, scales: torch.Tensor, x: torch.Tensor,
