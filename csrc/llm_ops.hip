@@ -2532,6 +2532,8 @@ extern "C" hipError_t launch_embed(const void* embed, const void* ids,
 // Sampling: greedy argmax or min-p + Gumbel-argmax multinomial.
 //   keep tokens with p >= min_p * p_max  <=>  logit >= max + ln(min_p);
 //   winner = argmax over kept of (logit + Gumbel noise).
+// top-k / top-p: the same pick over {fkey(logit) >= tau}, tau found by
+// the k_sample_select radix select (launch_sample_sel).
 // Writes the token to *next_token (feeds the next decode graph step),
 // appends to out_ring, bumps *len_ptr and *nout — all device-side, so the
 // whole decode step is graph-replayable.
@@ -2605,30 +2607,47 @@ k_logit_max(const void* __restrict__ logits, int V, int lbf16,
 // Temperature folds into both the min-p keep-set and the Gumbel score:
 //   p_i(T) >= min_p * p_max(T)  <=>  l_i >= l_max + T*ln(min_p)
 //   Gumbel-argmax over p(T)     <=>  argmax of l_i/T + G_i
-extern "C" __global__ void __launch_bounds__(256)
-k_sample_pick(const void* __restrict__ logits, int V, int lbf16,
-              long ring_stride, float min_p,
-              int greedy, uint64_t seed, float inv_temp,
-              unsigned long long* __restrict__ gmax,
-              uint64_t* __restrict__ ctr,
-              unsigned long long* __restrict__ pick,
-              int* __restrict__ cnt, int* __restrict__ next_token,
-              int* __restrict__ out_ring, int* __restrict__ nout,
-              int* __restrict__ len_ptr, int bump_len) {
+// SEL: the keep-set cut comes from the selection stage (k_sample_select)
+// as an fkey in sel[SEL_TAU] instead of the min-p expression; compared in
+// key space so the kept set is exactly the one the radix select counted.
+#define SEL_TAU 0     // out: threshold key tau (armed 0 = keep everything)
+#define SEL_PREFIX 1  // key bits fixed by the passes so far
+#define SEL_TARGET 2  // count / fixed-point mass still to cover in-bin
+#define SEL_TICKET 3  // last-arriver ticket of the running pass
+#define SEL_HIST 4    // 256-bin u64 histogram (count or fixed-point mass)
+#define SEL_WORDS 260
+
+template <bool SEL>
+DEVINL void sample_pick_body(
+    const void* __restrict__ logits, int V, int lbf16,
+    long ring_stride, float min_p,
+    int greedy, uint64_t seed, float inv_temp,
+    unsigned long long* __restrict__ gmax,
+    uint64_t* __restrict__ ctr,
+    unsigned long long* __restrict__ pick,
+    int* __restrict__ cnt, int* __restrict__ next_token,
+    int* __restrict__ out_ring, int* __restrict__ nout,
+    int* __restrict__ len_ptr, int bump_len,
+    unsigned long long* __restrict__ sel) {
   const int b = blockIdx.y;
   gmax += b; pick += b; cnt += b; nout += b;
   out_ring += (size_t)b * ring_stride;
   const float* lf = (const float*)logits + (size_t)b * V;
   const u16* lh = (const u16*)logits + (size_t)b * V;
   float thresh = -INFINITY;
-  if (!greedy)
+  uint32_t tau = 0;
+  if (SEL) {
+    sel += (size_t)b * SEL_WORDS;
+    tau = (uint32_t)sel[SEL_TAU];
+  } else if (!greedy) {
     thresh = fkey_inv((uint32_t)(*gmax >> 32)) + __logf(min_p) / inv_temp;
+  }
   const uint32_t c = (uint32_t)(*ctr) ^ ((uint32_t)b * 0x85ebca6bu);
   float bv = -INFINITY;
   int bi = 0x7fffffff;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < V; i += gridDim.x * 256) {
     float v = lbf16 ? b2f(lh[i]) : lf[i];
-    if (v < thresh) continue;
+    if (SEL ? (fkey(v) < tau) : (v < thresh)) continue;
     float sc = v;
     if (!greedy) {
       uint32_t r = hash32(hash32((uint32_t)i ^ (c * 0x9e3779b9u)) ^
@@ -2674,6 +2693,146 @@ k_sample_pick(const void* __restrict__ logits, int V, int lbf16,
   if (bump_len) len_ptr[b] += 1;
   *pick = 0ull;
   *gmax = 0ull;
+  if (SEL) {
+    sel[SEL_TAU] = 0ull;
+    sel[SEL_PREFIX] = 0ull;
+    sel[SEL_TARGET] = 0ull;
+  }
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+k_sample_pick(const void* __restrict__ logits, int V, int lbf16,
+              long ring_stride, float min_p,
+              int greedy, uint64_t seed, float inv_temp,
+              unsigned long long* __restrict__ gmax,
+              uint64_t* __restrict__ ctr,
+              unsigned long long* __restrict__ pick,
+              int* __restrict__ cnt, int* __restrict__ next_token,
+              int* __restrict__ out_ring, int* __restrict__ nout,
+              int* __restrict__ len_ptr, int bump_len) {
+  sample_pick_body<false>(logits, V, lbf16, ring_stride, min_p, greedy, seed,
+                          inv_temp, gmax, ctr, pick, cnt, next_token,
+                          out_ring, nout, len_ptr, bump_len, nullptr);
+}
+
+// top-k / top-p variant: same Gumbel pick, keep-set = {fkey(l) >= tau}
+extern "C" __global__ void __launch_bounds__(256)
+k_sample_pick_sel(const void* __restrict__ logits, int V, int lbf16,
+                  long ring_stride, uint64_t seed, float inv_temp,
+                  unsigned long long* __restrict__ gmax,
+                  uint64_t* __restrict__ ctr,
+                  unsigned long long* __restrict__ pick,
+                  int* __restrict__ cnt, int* __restrict__ next_token,
+                  int* __restrict__ out_ring, int* __restrict__ nout,
+                  int* __restrict__ len_ptr, int bump_len,
+                  unsigned long long* __restrict__ sel) {
+  sample_pick_body<true>(logits, V, lbf16, ring_stride, 0.0f, 0, seed,
+                         inv_temp, gmax, ctr, pick, cnt, next_token,
+                         out_ring, nout, len_ptr, bump_len, sel);
+}
+
+// Selection stage for top-k / top-p: one pass of an MSB-first radix
+// select over fkey(logit), 8 bits per pass (launched 4x: shift 24,16,8,0;
+// bf16 rows 2x: their keys' low 16 bits are zero, so bin 0 is known).
+// Both filters are "smallest suffix of the sorted row whose WEIGHT reaches
+// a target": weight 1 / target k for top-k; weight
+// w_i = exp((l_i - l_max) * inv_temp) in 2^40 fixed point / target
+// ceil(top_p * sum w) for top-p (integers: the sums do not depend on the
+// order the atomics arrive in, so tau is reproducible).  Each block
+// histograms the elements whose key matches the prefix found so far into
+// LDS, merges the non-empty bins into the row's global histogram, and the
+// last-arriving block (ticket) suffix-scans the 256 bins, descends into
+// the bin holding the boundary and re-zeroes histogram + ticket.  After
+// the `last` pass the prefix is the threshold key tau (ties at tau are
+// kept).  A row that cannot reach its target (all-NaN / zero mass) falls
+// to bin 0 every pass: tau = 0 keeps everything, nothing loops.
+extern "C" __global__ void __launch_bounds__(256)
+k_sample_select(const void* __restrict__ logits, int V, int lbf16,
+                int top_k, float top_p, float inv_temp, int shift,
+                int last, const unsigned long long* __restrict__ gmax,
+                unsigned long long* __restrict__ sel) {
+  const int b = blockIdx.y;
+  const int t = threadIdx.x;
+  sel += (size_t)b * SEL_WORDS;
+  unsigned long long* hist = sel + SEL_HIST;
+  const float* lf = (const float*)logits + (size_t)b * V;
+  const u16* lh = (const u16*)logits + (size_t)b * V;
+  __shared__ unsigned long long sh[256];
+  __shared__ int lastflag;
+  sh[t] = 0ull;
+  __syncthreads();
+  const bool first = shift == 24;
+  const uint32_t prefix = first ? 0u : (uint32_t)sel[SEL_PREFIX];
+  const uint32_t himask = first ? 0u : (0xffffffffu << (shift + 8));
+  const float lmax = fkey_inv((uint32_t)(gmax[b] >> 32));
+  for (int i = blockIdx.x * 256 + t; i < V; i += gridDim.x * 256) {
+    float v = lbf16 ? b2f(lh[i]) : lf[i];
+    uint32_t key = fkey(v);
+    if ((key & himask) != prefix) continue;
+    unsigned long long w = 1ull;
+    if (top_k == 0) {
+      float e = __expf((v - lmax) * inv_temp);
+      e = e >= 0.0f ? fminf(e, 1.0f) : 0.0f;  // NaN -> 0
+      w = (unsigned long long)(e * 1099511627776.0f);  // 2^40
+    }
+    if (w) atomicAdd(&sh[(key >> shift) & 255u], w);
+  }
+  __syncthreads();
+  // wave 0 merges all 256 bins, so ONE wave's release fence (an L2
+  // write-back) orders the whole block's contribution ahead of its
+  // ticket: measured 16 us/pass at B=8, 27 us when every wave fenced
+  // (profiles/sampler_select.md)
+  if (t < 64) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      unsigned long long hj = sh[t + 64 * j];
+      if (hj)
+        __hip_atomic_fetch_add(&hist[t + 64 * j], hj, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    if (t == 0) {
+      unsigned long long tk = __hip_atomic_fetch_add(
+          &sel[SEL_TICKET], 1ull, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+      lastflag = (tk == (unsigned long long)gridDim.x - 1);
+    }
+  }
+  __syncthreads();
+  if (!lastflag) return;
+  // last arriver: every block's bins are in; scan, descend, re-arm
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  unsigned long long h =
+      __hip_atomic_load(&hist[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  hist[t] = 0ull;
+  if (t == 0) sel[SEL_TICKET] = 0ull;
+  sh[t] = h;
+  __syncthreads();
+  // inclusive suffix sums: sh[t] = weight of all keys in bins >= t
+  for (int off = 1; off < 256; off <<= 1) {
+    unsigned long long a = (t + off < 256) ? sh[t + off] : 0ull;
+    __syncthreads();
+    sh[t] += a;
+    __syncthreads();
+  }
+  unsigned long long target;
+  if (!first) {
+    target = sel[SEL_TARGET];
+  } else if (top_k > 0) {
+    target = (unsigned long long)top_k;
+  } else {
+    target = (unsigned long long)ceil((double)top_p * (double)sh[0]);
+    if (target == 0ull) target = 1ull;
+  }
+  __syncthreads();  // everyone holds the old target before it is replaced
+  const unsigned long long above = (t < 255) ? sh[t + 1] : 0ull;
+  // exactly one bin: the highest whose suffix reaches the target (bin 0
+  // when none does)
+  if (above < target && (t == 0 || sh[t] >= target)) {
+    const uint32_t p = prefix | ((uint32_t)t << shift);
+    sel[SEL_PREFIX] = p;
+    sel[SEL_TARGET] = target - above;
+    if (last) sel[SEL_TAU] = p;
+  }
 }
 
 extern "C" hipError_t launch_sample(const void* logits, int V, int lbf16,
@@ -2702,6 +2861,51 @@ extern "C" hipError_t launch_sample(const void* logits, int V, int lbf16,
                      (unsigned long long*)gmax, (uint64_t*)ctr,
                      (unsigned long long*)pick, (int*)cnt, (int*)next_token,
                      (int*)out_ring, (int*)nout, (int*)len_ptr, bump_len);
+  return hipGetLastError();
+}
+
+// launch_sample + device-side top-k / top-p.  top_k > 0: keep the k
+// largest logits (ties at the k-th kept); else top_p < 1: keep the
+// smallest highest-probability prefix whose mass reaches top_p; neither
+// (or greedy): exactly launch_sample.  sel: SEL_WORDS u64 per row,
+// zeroed once, re-armed on device.
+extern "C" hipError_t launch_sample_sel(
+    const void* logits, int V, int lbf16, int batch, long ring_stride,
+    float min_p, int greedy, uint64_t seed, float inv_temp, void* ctr,
+    void* gmax, void* pick, void* cnt, void* next_token, void* out_ring,
+    void* nout, void* len_ptr, int bump_len, int top_k, float top_p,
+    void* sel, hipStream_t stream) {
+  if (greedy || (top_k <= 0 && !(top_p < 1.0f)))
+    return launch_sample(logits, V, lbf16, batch, ring_stride, min_p, greedy,
+                         seed, inv_temp, ctr, gmax, pick, cnt, next_token,
+                         out_ring, nout, len_ptr, bump_len, stream);
+  if (top_k > V) top_k = V;
+  int blocks = (V + 255) / 256;
+  if (blocks > 512) blocks = 512;
+  if (batch > 1) {
+    blocks = blocks / batch + 1;
+    if (blocks < 16) blocks = 16;
+  }
+  // few blocks per row: every block merges its bins into the same handful
+  // of hot histogram words, so the merge cost grows with the block count
+  int sblocks = (V + 2047) / 2048;
+  if (sblocks > 64) sblocks = 64;
+  hipLaunchKernelGGL(k_logit_max, dim3(blocks, batch), dim3(256), 0, stream,
+                     logits, V, lbf16, (unsigned long long*)gmax,
+                     (uint64_t*)ctr);
+  const int last_shift = lbf16 ? 16 : 0;
+  for (int shift = 24; shift >= last_shift; shift -= 8)
+    hipLaunchKernelGGL(k_sample_select, dim3(sblocks, batch), dim3(256), 0,
+                       stream, logits, V, lbf16, top_k, top_p, inv_temp,
+                       shift, shift == last_shift ? 1 : 0,
+                       (const unsigned long long*)gmax,
+                       (unsigned long long*)sel);
+  hipLaunchKernelGGL(k_sample_pick_sel, dim3(blocks, batch), dim3(256), 0,
+                     stream, logits, V, lbf16, ring_stride, seed, inv_temp,
+                     (unsigned long long*)gmax, (uint64_t*)ctr,
+                     (unsigned long long*)pick, (int*)cnt, (int*)next_token,
+                     (int*)out_ring, (int*)nout, (int*)len_ptr, bump_len,
+                     (unsigned long long*)sel);
   return hipGetLastError();
 }
 

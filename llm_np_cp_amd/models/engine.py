@@ -41,6 +41,11 @@ class DeviceCacheHandle:
 
 
 class GPUModel:
+    # sampling strategies the in-graph device sampler implements; the
+    # runtime (generate(), the server's batch scheduler) routes on this
+    device_strategies = frozenset(
+        {"greedy", "min_p", "top_k", "top_p", "temperature"})
+
     def __init__(self, config: ModelConfig, weights: Dict[str, np.ndarray],
                  dtype: str = "bf16", max_seq: Optional[int] = 4096,
                  prefill_chunk: int = 2048, device: Optional[str] = None,
@@ -416,6 +421,9 @@ class GPUModel:
         self.s_gmax = torch.zeros(1, dtype=torch.int64, device=dev)
         self.s_pick = torch.zeros(1, dtype=torch.int64, device=dev)
         self.s_cnt = torch.zeros(1, dtype=torch.int32, device=dev)
+        # top-k / top-p selection scratch (radix-select state + histogram)
+        self.s_sel = torch.zeros(1, ho.SAMPLE_SEL_WORDS, dtype=torch.int64,
+                                 device=dev)
         i32 = dict(dtype=torch.int32, device=dev)
         self.ids_buf = torch.zeros(PC, **i32)
         self.next_token = torch.zeros(1, **i32)
@@ -439,6 +447,7 @@ class GPUModel:
             self.bt_gmax = torch.zeros(B, **i64)
             self.bt_pick = torch.zeros(B, **i64)
             self.bt_cnt = torch.zeros(B, **i32)
+            self.bt_sel = torch.zeros(B, ho.SAMPLE_SEL_WORDS, **i64)
             self.bt_scratch = torch.zeros(
                 B * self.nh_l * self.attn_split * (hd + 2),
                 dtype=torch.float32, device=dev)
@@ -471,6 +480,7 @@ class GPUModel:
         self.s_gmax.zero_()
         self.s_pick.zero_()
         self.s_cnt.zero_()
+        self.s_sel.zero_()
         self._host_len = 0  # host mirror of len_buf (overflow guard)
 
     # ------------------------------------------------------------------
@@ -854,10 +864,13 @@ class GPUModel:
     def generate_tokens(self, prompt_ids, max_tokens: int,
                         greedy: bool = True, min_p: float = 0.1,
                         eos_id=None, chunk: int = 16, on_ids=None,
-                        temperature: float = 1.0, stop_fn=None):
+                        temperature: float = 1.0, stop_fn=None,
+                        top_k: int = 0, top_p: float = 1.0):
         """Fast generate: device-side hipGraph decode in chunks, host
         sees ids every `chunk` tokens (streaming + EOS stop).  Used by
-        runtime.generate() for greedy/min-p on GPU models.
+        runtime.generate() for every strategy in ``device_strategies``
+        (``top_k`` > 0 / ``top_p`` < 1 select the device-side filter; 0 /
+        1.0 = off).
         ``eos_id`` may be an int or a collection of ints (HF configs
         often store a list, e.g. Llama-3.2-Instruct).  ``stop_fn``
         (optional) sees the accumulated ids after each chunk and returns
@@ -885,7 +898,8 @@ class GPUModel:
                 n = min(chunk, max_tokens - produced)
                 ids = self.decode(n, greedy=greedy, min_p=min_p,
                                   use_graph=True, first_from_logits=first,
-                                  temperature=temperature)
+                                  temperature=temperature, top_k=top_k,
+                                  top_p=top_p)
                 first = False
                 produced += n
                 stop = False
@@ -956,7 +970,8 @@ class GPUModel:
         return (lw["wqkv"], lw["wo"], lw["wgu"], lw["wdown"])
 
     def _decode_step(self, greedy: bool, min_p: float,
-                     temperature: float = 1.0):
+                     temperature: float = 1.0, top_k: int = 0,
+                     top_p: float = 1.0):
         """Fused decode path: 4 kernels/layer (llama) or 5 (gemma) —
         RMSNorm lives inside the GEMV staging pass, RoPE + KV write
         inside the attention kernel.  bf16 weights: the gate+up GEMV
@@ -1117,13 +1132,15 @@ class GPUModel:
         ho.sample(self.b_logits, min_p, greedy, self.seed, self.rng_ctr,
                   self.s_gmax, self.s_pick, self.next_token, self.out_ring,
                   self.nout, self.len_buf, bump_len=True,
-                  temperature=temperature, cnt=self.s_cnt)
+                  temperature=temperature, cnt=self.s_cnt,
+                  top_k=top_k, top_p=top_p, sel=self.s_sel)
 
     # ------------------------------------------------------------------
     # lockstep batched decode (throughput mode; beyond-parity capability)
     # ------------------------------------------------------------------
     def _decode_batch_step(self, B: int, greedy: bool, min_p: float,
-                           temperature: float = 1.0):
+                           temperature: float = 1.0, top_k: int = 0,
+                           top_p: float = 1.0):
         """One decode step for B lockstep sequences.  fp8 weights with
         B<=8 take the fused MULTI-X GEMV path (one weight stream feeds
         B accumulators — near single-sequence step time); otherwise the
@@ -1139,10 +1156,12 @@ class GPUModel:
         mx_max = int(_os.environ.get("LLM_BATCH_MX_MAX", "0"))
         if (self.fp8 and B <= mx_max and not cfg.attention_bias
                 and not self.moe):
-            return self._decode_batch_step_mx(B, greedy, min_p, temperature)
+            return self._decode_batch_step_mx(B, greedy, min_p, temperature,
+                                              top_k, top_p)
         if self.fp8 and B <= 16 and not self.moe:
             return self._decode_batch_step_skinny(B, greedy, min_p,
-                                                  temperature)
+                                                  temperature, top_k,
+                                                  top_p)
         ho.embed(self.embed, self.bt_next, self.b_h, B, cfg.embed_scale)
         self._layers_forward(B, batch_attn=True)
         ho.rmsnorm(self.b_h[:B], self.g_final, self.b_xn[:B],
@@ -1160,10 +1179,12 @@ class GPUModel:
         ho.sample(self.bt_logits[:B], min_p, greedy, self.seed,
                   self.rng_ctr, self.bt_gmax, self.bt_pick, self.bt_next,
                   self.bt_ring, self.bt_nout, self.bt_lens, bump_len=True,
-                  temperature=temperature, cnt=self.bt_cnt, batch=B)
+                  temperature=temperature, cnt=self.bt_cnt, batch=B,
+                  top_k=top_k, top_p=top_p, sel=self.bt_sel)
 
     def _decode_batch_step_mx(self, B: int, greedy: bool, min_p: float,
-                              temperature: float = 1.0):
+                              temperature: float = 1.0, top_k: int = 0,
+                              top_p: float = 1.0):
         """Fused batched decode (fp8, B<=8): mirrors _decode_step's
         4-5 kernels/layer with multi-x GEMVs over B rows."""
         cfg = self.config
@@ -1239,10 +1260,12 @@ class GPUModel:
         ho.sample(self.bt_logits[:B], min_p, greedy, self.seed,
                   self.rng_ctr, self.bt_gmax, self.bt_pick, self.bt_next,
                   self.bt_ring, self.bt_nout, self.bt_lens, bump_len=True,
-                  temperature=temperature, cnt=self.bt_cnt, batch=B)
+                  temperature=temperature, cnt=self.bt_cnt, batch=B,
+                  top_k=top_k, top_p=top_p, sel=self.bt_sel)
 
     def _decode_batch_step_skinny(self, B: int, greedy: bool,
-                                  min_p: float, temperature: float = 1.0):
+                                  min_p: float, temperature: float = 1.0,
+                                  top_k: int = 0, top_p: float = 1.0):
         """Batched decode via (stage+quant, skinny fp8 MFMA GEMM) pairs:
         B = 3..16 lockstep rows, W streamed once per projection."""
         cfg = self.config
@@ -1328,7 +1351,8 @@ class GPUModel:
         ho.sample(self.bt_logits[:B], min_p, greedy, self.seed,
                   self.rng_ctr, self.bt_gmax, self.bt_pick, self.bt_next,
                   self.bt_ring, self.bt_nout, self.bt_lens, bump_len=True,
-                  temperature=temperature, cnt=self.bt_cnt, batch=B)
+                  temperature=temperature, cnt=self.bt_cnt, batch=B,
+                  top_k=top_k, top_p=top_p, sel=self.bt_sel)
 
     def prefill_batch(self, prompts) -> None:
         """Prefill B prompts (RAGGED lengths allowed) into per-sequence
@@ -1369,7 +1393,8 @@ class GPUModel:
     def decode_batch(self, n_tokens: int, greedy: bool = True,
                      min_p: float = 0.1, temperature: float = 1.0,
                      use_graph: bool = True,
-                     first_from_logits: bool = True) -> np.ndarray:
+                     first_from_logits: bool = True,
+                     top_k: int = 0, top_p: float = 1.0) -> np.ndarray:
         """Decode n_tokens for every prefilled sequence; returns int32
         ids of shape (B, n_tokens).  ``first_from_logits=False``
         continues a previous decode_batch (chunked serving)."""
@@ -1383,22 +1408,25 @@ class GPUModel:
                       self.rng_ctr, self.bt_gmax, self.bt_pick,
                       self.bt_next, self.bt_ring, self.bt_nout,
                       self.bt_lens, bump_len=False,
-                      temperature=temperature, cnt=self.bt_cnt, batch=B)
+                      temperature=temperature, cnt=self.bt_cnt, batch=B,
+                      top_k=top_k, top_p=top_p, sel=self.bt_sel)
         n_steps = n_tokens - (1 if first_from_logits else 0)
-        key = ("batch", B, greedy, min_p, temperature)
+        key = ("batch", B, greedy, min_p, temperature, top_k, top_p)
         if use_graph and n_steps > 0 and self._graph_mode != key \
                 and not getattr(self, "_graph_failed", False):
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
-                self._decode_batch_step(B, greedy, min_p, temperature)
+                self._decode_batch_step(B, greedy, min_p, temperature,
+                                        top_k, top_p)
             torch.cuda.current_stream().wait_stream(s)
             torch.cuda.synchronize()
             n_steps -= 1
             try:
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
-                    self._decode_batch_step(B, greedy, min_p, temperature)
+                    self._decode_batch_step(B, greedy, min_p, temperature,
+                                            top_k, top_p)
                 self._graph = g
                 self._graph_mode = key
             except Exception as e:
@@ -1410,7 +1438,8 @@ class GPUModel:
                 self._graph.replay()
         else:
             for _ in range(n_steps):
-                self._decode_batch_step(B, greedy, min_p, temperature)
+                self._decode_batch_step(B, greedy, min_p, temperature,
+                                        top_k, top_p)
         torch.cuda.synchronize()
         n = int(self.bt_nout[0].item())
         out = self.bt_ring[:B, :n].cpu().numpy()
@@ -1418,7 +1447,8 @@ class GPUModel:
 
     # ---- continuous batching primitives (rows join/leave the group) ----
     def prefill_row(self, b: int, ids, greedy: bool = True,
-                    min_p: float = 0.1, temperature: float = 1.0):
+                    min_p: float = 0.1, temperature: float = 1.0,
+                    top_k: int = 0, top_p: float = 1.0):
         """Prefill ONE sequence into slot b (other rows untouched) and
         sample its first token — a request JOINING the lockstep group
         between decode chunks (server continuous batching)."""
@@ -1450,7 +1480,8 @@ class GPUModel:
                   self.bt_next[b:b + 1], self.bt_ring[b:b + 1],
                   self.bt_nout[b:b + 1], self.bt_lens[b:b + 1],
                   bump_len=False, temperature=temperature,
-                  cnt=self.bt_cnt[b:b + 1], batch=1)
+                  cnt=self.bt_cnt[b:b + 1], batch=1,
+                  top_k=top_k, top_p=top_p, sel=self.bt_sel[b:b + 1])
         if not hasattr(self, "_host_lens") or self._host_lens is None:
             self._host_lens = [0] * self.max_batch
         while len(self._host_lens) < self.max_batch:
@@ -1477,7 +1508,8 @@ class GPUModel:
 
     def decode_rows(self, B: int, n: int, greedy: bool = True,
                     min_p: float = 0.1, temperature: float = 1.0,
-                    use_graph: bool = True):
+                    use_graph: bool = True, top_k: int = 0,
+                    top_p: float = 1.0):
         """n lockstep steps for rows [0, B) (each already holding a
         sampled next token from prefill_row / a previous chunk).
         Returns a list of B arrays: each row's n new token ids."""
@@ -1486,7 +1518,7 @@ class GPUModel:
             raise ValueError("decode_rows would overflow the KV pool")
         for b in range(B):
             self._host_lens[b] += n
-        key = ("batchc", B, greedy, min_p, temperature)
+        key = ("batchc", B, greedy, min_p, temperature, top_k, top_p)
         if not hasattr(self, "_bgraphs"):
             self._bgraphs = {}
         g = self._bgraphs.get(key)
@@ -1496,14 +1528,16 @@ class GPUModel:
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
-                self._decode_batch_step(B, greedy, min_p, temperature)
+                self._decode_batch_step(B, greedy, min_p, temperature,
+                                        top_k, top_p)
             torch.cuda.current_stream().wait_stream(s)
             torch.cuda.synchronize()
             executed += 1  # the warm-up was a real step
             try:
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
-                    self._decode_batch_step(B, greedy, min_p, temperature)
+                    self._decode_batch_step(B, greedy, min_p, temperature,
+                                            top_k, top_p)
                 self._bgraphs[key] = g
             except Exception as e:
                 self._graph_failed = True
@@ -1515,7 +1549,8 @@ class GPUModel:
                 g.replay()
         else:
             for _ in range(remaining):
-                self._decode_batch_step(B, greedy, min_p, temperature)
+                self._decode_batch_step(B, greedy, min_p, temperature,
+                                        top_k, top_p)
         torch.cuda.synchronize()
         comm = tpu.xgmi_comm()
         if comm is not None:
@@ -1528,14 +1563,17 @@ class GPUModel:
 
     def generate_tokens_batch(self, prompts, max_tokens: int,
                               greedy: bool = True, min_p: float = 0.1,
-                              temperature: float = 1.0) -> np.ndarray:
+                              temperature: float = 1.0, top_k: int = 0,
+                              top_p: float = 1.0) -> np.ndarray:
         """Convenience: prefill_batch + decode_batch -> (B, max_tokens)."""
         self.prefill_batch(prompts)
         return self.decode_batch(max_tokens, greedy=greedy, min_p=min_p,
-                                 temperature=temperature)
+                                 temperature=temperature, top_k=top_k,
+                                 top_p=top_p)
 
     def capture_decode_graph(self, greedy: bool = True, min_p: float = 0.1,
-                             temperature: float = 1.0):
+                             temperature: float = 1.0, top_k: int = 0,
+                             top_p: float = 1.0):
         """Capture one decode step into a hipGraph (fixed shapes: KV pool
         is preallocated and the position is a device scalar — SURVEY §7
         'graph must be shape-stable').
@@ -1548,7 +1586,7 @@ class GPUModel:
         capture failure ``ok`` is False, ``self._graph_failed`` is set
         (no further capture attempts) and the exception is kept in
         ``self._graph_error``."""
-        mode = (greedy, min_p, temperature)
+        mode = (greedy, min_p, temperature, top_k, top_p)
         if self._graph_mode == mode:
             return 0, True
         if getattr(self, "_graph_failed", False):
@@ -1557,13 +1595,13 @@ class GPUModel:
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
-            self._decode_step(greedy, min_p, temperature)
+            self._decode_step(greedy, min_p, temperature, top_k, top_p)
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
         try:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                self._decode_step(greedy, min_p, temperature)
+                self._decode_step(greedy, min_p, temperature, top_k, top_p)
         except Exception as e:
             # the warm-up step above DID run (token committed to
             # out_ring, len_buf advanced) — report it so decode() does
@@ -1584,7 +1622,8 @@ class GPUModel:
 
     def decode(self, n_tokens: int, greedy: bool = True, min_p: float = 0.1,
                use_graph: bool = True, first_from_logits: bool = True,
-               temperature: float = 1.0):
+               temperature: float = 1.0, top_k: int = 0,
+               top_p: float = 1.0):
         """Generate n_tokens ids device-side; returns int32 numpy ids.
         Assumes prefill() ran (len_buf == prompt length, logits ready)."""
         if getattr(self, "_host_len", 0) + n_tokens > self.max_seq:
@@ -1598,12 +1637,14 @@ class GPUModel:
                       self.s_gmax, self.s_pick, self.next_token,
                       self.out_ring, self.nout, self.len_buf,
                       bump_len=False, temperature=temperature,
-                      cnt=self.s_cnt)
+                      cnt=self.s_cnt, top_k=top_k, top_p=top_p,
+                      sel=self.s_sel)
         n_steps = n_tokens - (1 if first_from_logits else 0)
         if use_graph and n_steps > 0:
             # capture_decode_graph reports the warm-up step it executed
             # even when capture fails, so n_steps stays exact either way
-            taken, ok = self.capture_decode_graph(greedy, min_p, temperature)
+            taken, ok = self.capture_decode_graph(greedy, min_p, temperature,
+                                                  top_k, top_p)
             n_steps -= taken
             if not ok:
                 use_graph = False
@@ -1612,7 +1653,7 @@ class GPUModel:
                 self._graph.replay()
         else:
             for _ in range(n_steps):
-                self._decode_step(greedy, min_p, temperature)
+                self._decode_step(greedy, min_p, temperature, top_k, top_p)
         torch.cuda.synchronize()
         comm = tpu.xgmi_comm()
         if comm is not None:

@@ -58,6 +58,12 @@ _SIGS = {
                       ctypes.c_int, ctypes.c_uint64, ctypes.c_float] +
                      [ctypes.c_void_p] * 8 +
                      [ctypes.c_int, ctypes.c_void_p],
+    "launch_sample_sel": [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                          ctypes.c_int, ctypes.c_long, ctypes.c_float,
+                          ctypes.c_int, ctypes.c_uint64, ctypes.c_float] +
+                         [ctypes.c_void_p] * 8 +
+                         [ctypes.c_int, ctypes.c_int, ctypes.c_float,
+                          ctypes.c_void_p, ctypes.c_void_p],
     "launch_gemm_bf16": [ctypes.c_void_p] * 5 + [ctypes.c_int] * 3 +
                         [ctypes.c_void_p],
     "launch_prefetch": [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p,
@@ -320,18 +326,46 @@ def embed(table: torch.Tensor, ids: torch.Tensor, out: torch.Tensor,
                               ctypes.c_float(scale), _stream()), "embed")
 
 
+# u64 words of selection scratch per row (SEL_WORDS in csrc/llm_ops.hip):
+# tau, prefix, target, ticket + a 256-bin histogram
+SAMPLE_SEL_WORDS = 260
+
+
 def sample(logits: torch.Tensor, min_p: float, greedy: bool, seed: int,
            ctr: torch.Tensor, gmax: torch.Tensor, pick: torch.Tensor,
            next_token: torch.Tensor, out_ring: torch.Tensor,
            nout: torch.Tensor, len_ptr: torch.Tensor,
            bump_len: bool = True, temperature: float = 1.0,
-           cnt: torch.Tensor | None = None, batch: int = 1):
+           cnt: torch.Tensor | None = None, batch: int = 1, *,
+           top_k: int = 0, top_p: float = 1.0,
+           sel: torch.Tensor | None = None):
     """min-p / greedy sampler: parallel max + Gumbel-argmax; the
     last-arriving pick block commits the winner (no 1-thread fin
     launch).  gmax/pick are u64 scratch (zeroed once; the commit path
     re-zeros); cnt is an i32 ticket counter (zeroed once, re-armed).
     Temperature scales device-side (min-p keep-set + Gumbel score), so
-    the GPU fast path matches the CPU sample_token() semantics."""
+    the GPU fast path matches the CPU sample_token() semantics.
+
+    ``top_k`` > 0 or ``top_p`` < 1 (one of them; 0 / 1.0 = off) replace
+    the min-p cut by a device-side radix select of the keep-set
+    threshold (``filter_probs`` semantics; ``min_p`` is then unused).
+    ``sel`` is its scratch: int64, ``SAMPLE_SEL_WORDS`` per row, zeroed
+    once and re-armed on device.  With both filters off the launch is
+    exactly the min-p / greedy one."""
+    if top_k < 0:
+        raise ValueError(f"top_k must be >= 0, got {top_k}")
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError(f"top_p must be in (0, 1], got {top_p}")
+    filtered = top_k > 0 or top_p < 1.0
+    if filtered and greedy:
+        raise ValueError("top_k / top_p do not combine with greedy")
+    if top_k > 0 and top_p < 1.0:
+        raise ValueError("top_k and top_p are separate strategies; "
+                         "pass one of them")
+    if filtered and (sel is None or sel.dtype != torch.int64
+                     or sel.numel() < batch * SAMPLE_SEL_WORDS):
+        raise ValueError(f"top_k / top_p need an int64 `sel` scratch of "
+                         f"{SAMPLE_SEL_WORDS} words per row")
     V = logits.shape[-1]
     lbf16 = 1 if logits.dtype == torch.bfloat16 else 0
     ring_stride = out_ring.shape[-1] if out_ring.dim() > 1 else 0
@@ -351,6 +385,16 @@ def sample(logits: torch.Tensor, min_p: float, greedy: bool, seed: int,
                                            device=logits.device)
         cnt = _SAMPLE_CNT[key]
     inv_temp = 1.0 / max(float(temperature), 1e-6)
+    if filtered:
+        _check(lib().launch_sample_sel(
+            _ptr(logits), V, lbf16, batch, ctypes.c_long(ring_stride),
+            ctypes.c_float(min_p), 0,
+            ctypes.c_uint64(seed), ctypes.c_float(inv_temp),
+            _ptr(ctr), _ptr(gmax), _ptr(pick), _ptr(cnt),
+            _ptr(next_token), _ptr(out_ring), _ptr(nout), _ptr(len_ptr),
+            1 if bump_len else 0, int(top_k), ctypes.c_float(top_p),
+            _ptr(sel), _stream()), "sample_sel")
+        return
     _check(lib().launch_sample(
         _ptr(logits), V, lbf16, batch, ctypes.c_long(ring_stride),
         ctypes.c_float(min_p), 1 if greedy else 0,

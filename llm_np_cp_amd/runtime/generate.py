@@ -23,7 +23,7 @@ from typing import Callable, List, Optional
 
 import numpy as np
 
-from .sampling import SamplingParams, sample_token
+from .sampling import SamplingParams, device_sampler_kwargs, sample_token
 
 
 @dataclass
@@ -140,8 +140,10 @@ def generate(prompt: str, tokenizer, model, max_tokens: int = 200,
     Seeds: the GPU fast path's device sampler derives its stream from
     the ENGINE seed + a device counter (baked into the captured graph),
     so ``params.seed`` is honored on the logits-visible paths (CPU
-    oracle; logprobs / logit_bias / top-k / top-p requests) but not by
-    the in-graph device sampler."""
+    oracle; logprobs / logit_bias requests; strategies the engine does
+    not list in ``device_strategies``) but not by the in-graph device
+    sampler — on an engine that advertises them that now includes
+    top-k / top-p / temperature, as it always did min-p."""
     params = params or SamplingParams()
     rng = np.random.default_rng(params.seed)
     prompt_ids = list(tokenizer.encode(prompt))
@@ -170,11 +172,14 @@ def generate(prompt: str, tokenizer, model, max_tokens: int = 200,
             return ids, text, "stop" if (hit or hit_eos) else "length"
         return ids, tokenizer.decode(ids), "stop" if hit_eos else "length"
 
-    # fast path: device-side chunked decode loop (GPU engine, greedy or
-    # min-p, cached mode) — same sampler semantics, device RNG
+    # fast path: device-side chunked decode loop (GPU engine, a strategy
+    # its device sampler implements, cached mode) — same sampler
+    # semantics, device RNG.  Engines that do not advertise
+    # device_strategies get greedy / min-p only, with the original kwargs.
     if (use_cache and logprobs is None and not params.logit_bias
             and hasattr(model, "generate_tokens")
-            and params.strategy in ("greedy", "min_p")):
+            and params.strategy in getattr(model, "device_strategies",
+                                           ("greedy", "min_p"))):
         t0 = time.perf_counter()
 
         def _emit(ids_chunk):
@@ -189,10 +194,9 @@ def generate(prompt: str, tokenizer, model, max_tokens: int = 200,
 
         ids = model.generate_tokens(
             prompt_ids, max_tokens,
-            greedy=params.strategy == "greedy", min_p=params.min_p,
             eos_id=eos_set if stop_on_eos else None, on_ids=_emit,
-            temperature=params.temperature,
-            stop_fn=_stop_fn if stops else None)
+            stop_fn=_stop_fn if stops else None,
+            **device_sampler_kwargs(params))
         dt = time.perf_counter() - t0
         tp = getattr(model, "last_prefill_time_s", 0.0)
         hit_eos = bool(ids) and stop_on_eos and int(ids[-1]) in eos_set

@@ -84,6 +84,31 @@ def filter_probs(logits: np.ndarray, params: SamplingParams) -> np.ndarray:
     return probs / probs.sum()
 
 
+def device_sampler_kwargs(params: SamplingParams) -> dict:
+    """Engine keyword arguments (``generate_tokens`` / ``prefill_row`` /
+    ``decode_rows``) that make the in-graph device sampler draw from the
+    distribution ``filter_probs`` defines for ``params``.  greedy and
+    min_p yield exactly ``greedy`` / ``min_p`` / ``temperature``, so
+    engines that predate the device-side filters keep working; the filter
+    keys appear only for the strategies that need them.  (``seed`` and
+    ``logit_bias`` have no device counterpart — callers keep such
+    requests on the host path.)"""
+    kw = dict(greedy=params.strategy == "greedy", min_p=params.min_p,
+              temperature=params.temperature)
+    if params.strategy in ("greedy", "min_p"):
+        return kw
+    kw["min_p"] = 0.0  # empty min-p cut: the whole vocabulary stays
+    if params.strategy == "top_k":
+        kw["top_k"] = max(1, int(params.top_k))
+    elif params.strategy == "top_p":
+        if not 0.0 < params.top_p:
+            raise ValueError(f"top_p must be > 0, got {params.top_p}")
+        kw["top_p"] = min(1.0, float(params.top_p))
+    elif params.strategy != "temperature":
+        raise ValueError(f"unknown sampling strategy {params.strategy!r}")
+    return kw
+
+
 def sample_token(logits: np.ndarray, params: SamplingParams,
                  rng: Optional[np.random.Generator] = None) -> int:
     """logits: (vocab,) fp32. Returns a token id (int)."""

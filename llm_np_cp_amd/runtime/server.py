@@ -13,8 +13,10 @@ device positions).  Between 16-token chunks, finished rows RETIRE (EOS
 or per-request max_tokens; the last row compacts into the freed slot)
 and queued compatible requests JOIN mid-flight (``prefill_row`` into a
 free slot) — continuous batching, not fixed groups.  Requests with
-CPU-only sampling strategies (top_k/top_p) or a non-batch engine fall
-back to single-sequence generate().
+sampling strategies the engine's device sampler does not implement
+(``device_strategies``; top_k/top_p/temperature on engines without the
+selection stage) or a non-batch engine fall back to single-sequence
+generate().
 
     python -m llm_np_cp_amd.runtime.server --model llama-3.2-1b \
         --port 8080 --max-batch 8
@@ -43,6 +45,8 @@ try:  # pydantic model must live at module scope (ForwardRef resolution)
         max_tokens: int = Field(128, ge=1)
         temperature: float = Field(1.0, gt=0)
         min_p: float = Field(0.1, ge=0, le=1)
+        top_k: int = Field(50, ge=1)
+        top_p: float = Field(0.9, gt=0, le=1)
         strategy: _Strategy = "min_p"
         seed: Optional[int] = None
         stop_on_eos: bool = True
@@ -62,6 +66,8 @@ try:  # pydantic model must live at module scope (ForwardRef resolution)
         max_tokens: int = Field(128, ge=1)
         temperature: float = Field(1.0, gt=0)
         min_p: float = Field(0.1, ge=0, le=1)
+        top_k: int = Field(50, ge=1)
+        top_p: float = Field(0.9, gt=0, le=1)
         strategy: _Strategy = "min_p"
         seed: Optional[int] = None
         stop_on_eos: bool = True
@@ -96,8 +102,11 @@ class BatchScheduler:
     compatible concurrent requests."""
 
     def __init__(self, generate_one, run_group, max_batch: int,
-                 window_s: float = 0.004):
+                 window_s: float = 0.004,
+                 device_strategies=("greedy", "min_p")):
         self.generate_one = generate_one
+        # strategies run_group's engine samples on device (lockstep group)
+        self.device_strategies = frozenset(device_strategies)
         self.run_group = run_group  # (pendings, poll_fn) -> resolves them
         self.max_batch = max_batch
         self.window_s = window_s
@@ -125,13 +134,16 @@ class BatchScheduler:
     @staticmethod
     def _key(req):
         return (req.strategy, round(req.min_p, 6),
-                round(req.temperature, 6), req.stop_on_eos)
+                round(req.temperature, 6), req.stop_on_eos,
+                getattr(req, "top_k", 50),
+                round(getattr(req, "top_p", 0.9), 6))
 
     def _batchable(self, req) -> bool:
         # streaming and stop-string requests take the generate_one
         # path (per-token callback / text-level truncation); the
         # lockstep group only surfaces ids per chunk
-        return (self.max_batch > 1 and req.strategy in ("greedy", "min_p")
+        return (self.max_batch > 1
+                and req.strategy in self.device_strategies
                 and not getattr(req, "stream", False)
                 and not getattr(req, "stop", None)
                 and getattr(req, "logprobs", None) is None
@@ -238,6 +250,7 @@ def build_app(model_name: str = "llama-3.2-1b", backend: str = "auto",
     from fastapi import Body, FastAPI
 
     import llm_np_cp_amd as L
+    from .sampling import device_sampler_kwargs
 
     tok, model, cfg = L.load_model(model_name, backend=backend,
                                    dtype=dtype, max_seq=max_seq,
@@ -307,6 +320,8 @@ def build_app(model_name: str = "llama-3.2-1b", backend: str = "auto",
             params = L.SamplingParams(
                 strategy=req.strategy, min_p=req.min_p,
                 temperature=req.temperature, seed=seed,
+                top_k=getattr(req, "top_k", 50),
+                top_p=getattr(req, "top_p", 0.9),
                 logit_bias={int(k): float(vv) for k, vv in bias.items()}
                 if bias else None)
             out = L.generate(req.prompt, tok, model,
@@ -361,15 +376,19 @@ def build_app(model_name: str = "llama-3.2-1b", backend: str = "auto",
                 p.done.set()
             return
         r0 = pendings[0].req
-        greedy = r0.strategy == "greedy"
-        min_p, temp, stop_eos = r0.min_p, r0.temperature, r0.stop_on_eos
+        stop_eos = r0.stop_on_eos
+        # one sampler setting per group (_key keeps groups homogeneous)
+        skw = device_sampler_kwargs(L.SamplingParams(
+            strategy=r0.strategy, min_p=r0.min_p,
+            temperature=r0.temperature,
+            top_k=getattr(r0, "top_k", 50),
+            top_p=getattr(r0, "top_p", 0.9)))
         rows: list = []  # slot -> _Row
 
         def admit(p):
             slot = len(rows)
             t_p = time.time()
-            model.prefill_row(slot, tok.encode(p.req.prompt),
-                              greedy=greedy, min_p=min_p, temperature=temp)
+            model.prefill_row(slot, tok.encode(p.req.prompt), **skw)
             p.prefill_s = time.time() - t_p
             rows.append(_Row(p))
             stats["requests"] += 1
@@ -405,8 +424,7 @@ def build_app(model_name: str = "llama-3.2-1b", backend: str = "auto",
                 rows[longest] = rows[B - 1]
                 rows.pop()
                 continue
-            out = model.decode_rows(B, chunk, greedy=greedy, min_p=min_p,
-                                    temperature=temp)
+            out = model.decode_rows(B, chunk, **skw)
             # the first sampled token (from prefill_row) precedes chunk 1
             for b in range(B):
                 row = rows[b]
@@ -443,7 +461,10 @@ def build_app(model_name: str = "llama-3.2-1b", backend: str = "auto",
 
     sched = BatchScheduler(generate_one, run_group,
                            max_batch if can_batch else 1,
-                           window_s=batch_window_ms / 1e3)
+                           window_s=batch_window_ms / 1e3,
+                           device_strategies=getattr(
+                               model, "device_strategies",
+                               ("greedy", "min_p")))
     app = FastAPI(title="llm_np_cp_amd", version=L.__version__)
 
     @app.get("/v1/models")
@@ -540,6 +561,7 @@ def build_app(model_name: str = "llama-3.2-1b", backend: str = "auto",
             prompt=chat_prompt(tok, req.messages),
             max_tokens=req.max_tokens,
             temperature=req.temperature, min_p=req.min_p,
+            top_k=req.top_k, top_p=req.top_p,
             strategy=req.strategy, seed=req.seed,
             stop_on_eos=req.stop_on_eos, stream=req.stream,
             stop=req.stop, logprobs=req.logprobs, n=req.n,

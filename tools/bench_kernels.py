@@ -120,6 +120,15 @@ def main():
     us = time_graph(lambda: ho.sample(logits, 0.1, False, 0, ctr, gmax, pick,
                                       nt_, ring, nout, ln))
     print(f"sample min-p  V={V}: {us:.2f}us")
+    sel = torch.zeros(ho.SAMPLE_SEL_WORDS, dtype=torch.int64, device=dev)
+    us = time_graph(lambda: ho.sample(logits, 0.0, False, 0, ctr, gmax, pick,
+                                      nt_, ring, nout, ln, top_k=50,
+                                      sel=sel))
+    print(f"sample top-k  V={V}: {us:.2f}us")
+    us = time_graph(lambda: ho.sample(logits, 0.0, False, 0, ctr, gmax, pick,
+                                      nt_, ring, nout, ln, top_p=0.9,
+                                      sel=sel))
+    print(f"sample top-p  V={V}: {us:.2f}us")
 
 
 if __name__ == "__main__" and "--layersim" not in sys.argv:
