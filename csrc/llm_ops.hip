@@ -1951,6 +1951,38 @@ k_attn_dec_t(const u16* __restrict__ qkv, void* __restrict__ kc,
   const u16* qh = qkv + (size_t)h * hd;
   const u16* kh = qkv + (size_t)(nh + kvhead) * hd;
   const u16* vh = qkv + (size_t)(nh + kvh + kvhead) * hd;
+  const u16* K0 = (const u16*)kc + (size_t)kvhead * S * hd;
+  const u16* V0 = (const u16*)vc + (size_t)kvhead * S * hd;
+  const uint8_t* K08 = (const uint8_t*)kc + (size_t)kvhead * S * hd;
+  const uint8_t* V08 = (const uint8_t*)vc + (size_t)kvhead * S * hd;
+  const float* kS0 = KV8 ? kS + (size_t)kvhead * S : nullptr;
+  const float* vS0 = KV8 ? vS + (size_t)kvhead * S : nullptr;
+
+  // history loads of iteration tt of this wave's scan (positions tt+p);
+  // nothing is loaded past the chunk (tt >= c1 leaves the outputs alone)
+  auto ldkv = [&](int tt, bool& vld, s8v& ko, s8v& vo,
+                  unsigned long long& kro, unsigned long long& vro,
+                  float& kso, float& vso) {
+    vld = false;
+    if (tt < c1) {
+      int t_ = tt + p;
+      vld = t_ < c1;
+      int tl_ = vld ? t_ : c0;
+      if (KV8) {
+        kro = *(const unsigned long long*)(K08 + (size_t)tl_ * hd + d0);
+        vro = *(const unsigned long long*)(V08 + (size_t)tl_ * hd + d0);
+        kso = kS0[tl_]; vso = vS0[tl_];
+      } else {
+        ko = *(const s8v*)(K0 + (size_t)tl_ * hd + d0);
+        vo = *(const s8v*)(V0 + (size_t)tl_ * hd + d0);
+      }
+    }
+  };
+  s8v kv{}, vv{}, kvn{}, vvn{};
+  unsigned long long kraw = 0, vraw = 0, krawn = 0, vrawn = 0;
+  float ksc = 1.f, vsc = 1.f, kscn = 1.f, vscn = 1.f;
+  bool valid, validn;
+
   float qf[8], kn[8], vn[8];
   {
     const bool lo = d0 < hd2;
@@ -1965,6 +1997,17 @@ k_attn_dec_t(const u16* __restrict__ qkv, void* __restrict__ kc,
     f4v c1v = *(const f4v*)(cp + ci + 4);
     f4v s0v = *(const f4v*)(sp + ci);
     f4v s1v = *(const f4v*)(sp + ci + 4);
+    // The first two iterations' K/V history go out here, behind the
+    // new token's loads and ahead of the RoPE arithmetic and the pool
+    // write: [c0, c1) never contains pos, so the write cannot feed
+    // them, and their (cold) miss overlaps the cos/sin/qkv miss.
+    // vmcnt retires in order: the arithmetic below waits for the loads
+    // above only.
+    {
+      const int t0 = c0 + wave * PP;
+      ldkv(t0, valid, kv, vv, kraw, vraw, ksc, vsc);
+      ldkv(t0 + 4 * PP, validn, kvn, vvn, krawn, vrawn, kscn, vscn);
+    }
     const float sgn = lo ? -1.f : 1.f;
 #pragma unroll
     for (int j = 0; j < 8; j++) {
@@ -1975,13 +2018,6 @@ k_attn_dec_t(const u16* __restrict__ qkv, void* __restrict__ kc,
       vn[j] = b2f(((u16*)&va)[j]);
     }
   }
-  const u16* K0 = (const u16*)kc + (size_t)kvhead * S * hd;
-  const u16* V0 = (const u16*)vc + (size_t)kvhead * S * hd;
-  const uint8_t* K08 = (const uint8_t*)kc + (size_t)kvhead * S * hd;
-  const uint8_t* V08 = (const uint8_t*)vc + (size_t)kvhead * S * hd;
-  const float* kS0 = KV8 ? kS + (size_t)kvhead * S : nullptr;
-  const float* vS0 = KV8 ? vS + (size_t)kvhead * S : nullptr;
-
   if (last_chunk && h == kvhead * grp && wave == 0 && p == 0) {
     if (KV8) {
       // per-(head,pos) absmax across the LP lanes (each holds 8 dims)
@@ -1995,15 +2031,16 @@ k_attn_dec_t(const u16* __restrict__ qkv, void* __restrict__ kc,
         kam = fmaxf(kam, __shfl_xor(kam, w));
         vam = fmaxf(vam, __shfl_xor(vam, w));
       }
-      float ksc = fmaxf(kam, 1e-8f) / 448.0f;
-      float vsc = fmaxf(vam, 1e-8f) / 448.0f;
+      // the new token's scales (ksc / vsc hold the prefetched history's)
+      const float knsc = fmaxf(kam, 1e-8f) / 448.0f;
+      const float vnsc = fmaxf(vam, 1e-8f) / 448.0f;
       *(unsigned long long*)((uint8_t*)kc +
-          ((size_t)kvhead * S + pos) * hd + d0) = f32x8_to_fp8(kn, 1.f / ksc);
+          ((size_t)kvhead * S + pos) * hd + d0) = f32x8_to_fp8(kn, 1.f / knsc);
       *(unsigned long long*)((uint8_t*)vc +
-          ((size_t)kvhead * S + pos) * hd + d0) = f32x8_to_fp8(vn, 1.f / vsc);
+          ((size_t)kvhead * S + pos) * hd + d0) = f32x8_to_fp8(vn, 1.f / vnsc);
       if (lane == 0) {
-        kS[(size_t)kvhead * S + pos] = ksc;
-        vS[(size_t)kvhead * S + pos] = vsc;
+        kS[(size_t)kvhead * S + pos] = knsc;
+        vS[(size_t)kvhead * S + pos] = vnsc;
       }
     } else {
       u16 ko[8], vo[8];
@@ -2026,31 +2063,8 @@ k_attn_dec_t(const u16* __restrict__ qkv, void* __restrict__ kc,
     if (t0 < c1) {
       // 2-AHEAD software pipeline: K/V for iterations i+1 and i+2 are
       // in flight while iteration i computes (the serial
-      // K->dot->softmax->V chain is the latency bound at small T)
-      auto ldkv = [&](int tt, bool& vld, s8v& ko, s8v& vo,
-                      unsigned long long& kro, unsigned long long& vro,
-                      float& kso, float& vso) {
-        vld = false;
-        if (tt < c1) {
-          int t_ = tt + p;
-          vld = t_ < c1;
-          int tl_ = vld ? t_ : c0;
-          if (KV8) {
-            kro = *(const unsigned long long*)(K08 + (size_t)tl_ * hd + d0);
-            vro = *(const unsigned long long*)(V08 + (size_t)tl_ * hd + d0);
-            kso = kS0[tl_]; vso = vS0[tl_];
-          } else {
-            ko = *(const s8v*)(K0 + (size_t)tl_ * hd + d0);
-            vo = *(const s8v*)(V0 + (size_t)tl_ * hd + d0);
-          }
-        }
-      };
-      s8v kv{}, vv{}, kvn{}, vvn{};
-      unsigned long long kraw = 0, vraw = 0, krawn = 0, vrawn = 0;
-      float ksc = 1.f, vsc = 1.f, kscn = 1.f, vscn = 1.f;
-      bool valid, validn;
-      ldkv(t0, valid, kv, vv, kraw, vraw, ksc, vsc);
-      ldkv(t0 + 4 * PP, validn, kvn, vvn, krawn, vrawn, kscn, vscn);
+      // K->dot->softmax->V chain is the latency bound at small T);
+      // iterations 0 and 1 were issued at the top of the kernel
       for (; t0 < c1; t0 += 4 * PP) {
         s8v kv2{}, vv2{};
         unsigned long long kraw2 = 0, vraw2 = 0;
