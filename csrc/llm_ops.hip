@@ -2924,6 +2924,196 @@ extern "C" hipError_t launch_sample_sel(
 }
 
 // ====================================================================
+// Logit processors: repetition / frequency / presence penalties and
+// logit_bias, applied IN PLACE to the logits row the sampler reads next
+// (after the lm_head's softcap, before temperature / any filter).
+// Per-row device state, so rows with different settings share one graph:
+//   stat [rows, V] i32  bit 30 (TOKSTAT_PROMPT): id occurs in the prompt;
+//                       low 30 bits: times the id was generated
+//   proc [rows, 4] f32  {repetition r, frequency f, presence p, bias_on}
+//   bias [rows, V] f32  dense logit_bias (read only when bias_on != 0)
+// Order per element i (runtime/sampling.py apply_logit_processors):
+//   stat != 0:  l = l > 0 ? l / r : l * r
+//   count c>0:  l -= f * c + p
+//   bias_on:    l += bias[i]
+// ====================================================================
+#define TOKSTAT_PROMPT 0x40000000
+#define TOKSTAT_COUNT 0x3fffffff
+
+// prompt ids -> flag words of one freshly zeroed stat row.  Every writer
+// of a word stores the same value, so duplicates need no atomics.
+extern "C" __global__ void __launch_bounds__(256)
+k_tokstat_mark(int* __restrict__ stat_row, const int* __restrict__ ids,
+               int n, int V) {
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const int t = ids[i];
+    if (t >= 0 && t < V) stat_row[t] = TOKSTAT_PROMPT;
+  }
+}
+
+DEVINL float logit_adjust_val(float l, int s, float r, float f, float p,
+                              float bv) {
+  if (s != 0) {
+    l = l > 0.0f ? l / r : l * r;
+    const int c = s & TOKSTAT_COUNT;
+    if (c) l -= f * (float)c + p;
+  }
+  return l + bv;
+}
+
+// one element, any alignment: row heads / tails and misaligned rows
+template <bool BF>
+DEVINL void logit_adjust_elem(void* lrow, int* srow, const float* brow,
+                              int i, int tok, float r, float f, float p,
+                              bool bias_on) {
+  int s = srow[i];
+  if (i == tok) { s += 1; srow[i] = s; }
+  const float bv = bias_on ? brow[i] : 0.0f;
+  if (s == 0 && bv == 0.0f) return;
+  if (BF) {
+    u16* lh = (u16*)lrow;
+    lh[i] = f2b(logit_adjust_val(b2f(lh[i]), s, r, f, p, bv));
+  } else {
+    float* lf = (float*)lrow;
+    lf[i] = logit_adjust_val(lf[i], s, r, f, p, bv);
+  }
+}
+
+// The dense pass over stat doubles as the history update: with
+// count_input the one thread that owns element next_token[b] (the token
+// the previous sampler launch committed) bumps its count before using it
+// — no atomics, no ordering between blocks, the sampler kernels untouched.
+// Groups of G elements (16 B of logits per lane) whose stat words are all
+// zero and that carry no bias never load their logits; touched elements
+// are stored one by one, so untouched neighbours keep their bits.
+template <bool BF>
+DEVINL void logit_adjust_body(void* logits, int V, int* stat,
+                              const float* proc, const float* bias,
+                              const int* next_token, int count_input) {
+  constexpr int G = BF ? 8 : 4;
+  const int b = blockIdx.y;
+  const float r = proc[b * 4 + 0];
+  const float f = proc[b * 4 + 1];
+  const float p = proc[b * 4 + 2];
+  const bool bias_on = proc[b * 4 + 3] != 0.0f;
+  if (r == 1.0f && f == 0.0f && p == 0.0f && !bias_on) return;  // identity
+  const int tok = count_input ? next_token[b] : -1;
+  const size_t row0 = (size_t)b * V;
+  int* srow = stat + row0;
+  const float* brow = bias + row0;
+  void* lrow = BF ? (void*)((u16*)logits + row0)
+                  : (void*)((float*)logits + row0);
+  const int tid = blockIdx.x * 256 + threadIdx.x;
+  const int nthr = gridDim.x * 256;
+  // element h is the first whose logits AND stat / bias words sit on a
+  // 16 B boundary (bf16 rows with odd V start 2-byte aligned); unaligned
+  // base pointers take the scalar path for the whole row
+  const bool aligned = (((uintptr_t)logits | (uintptr_t)stat |
+                         (uintptr_t)bias) & 15) == 0;
+  int h = aligned ? (int)((G - row0 % G) % G) : V;
+  if (h > V) h = V;
+  const int ngroups = (V - h) / G;
+  const int t0 = h + ngroups * G;
+  for (int i = tid; i < h; i += nthr)
+    logit_adjust_elem<BF>(lrow, srow, brow, i, tok, r, f, p, bias_on);
+  for (int i = t0 + tid; i < V; i += nthr)
+    logit_adjust_elem<BF>(lrow, srow, brow, i, tok, r, f, p, bias_on);
+  for (int g = tid; g < ngroups; g += nthr) {
+    const int i0 = h + g * G;
+    int s[G];
+    float bv[G];
+#pragma unroll
+    for (int q = 0; q < G / 4; q++) {
+      const int4 sv = *(const int4*)(srow + i0 + 4 * q);
+      s[4 * q + 0] = sv.x; s[4 * q + 1] = sv.y;
+      s[4 * q + 2] = sv.z; s[4 * q + 3] = sv.w;
+    }
+    if (tok >= i0 && tok < i0 + G) {
+#pragma unroll
+      for (int j = 0; j < G; j++)
+        if (i0 + j == tok) { s[j] += 1; srow[tok] = s[j]; }
+    }
+    if (bias_on) {
+#pragma unroll
+      for (int q = 0; q < G / 4; q++) {
+        const float4 b4 = *(const float4*)(brow + i0 + 4 * q);
+        bv[4 * q + 0] = b4.x; bv[4 * q + 1] = b4.y;
+        bv[4 * q + 2] = b4.z; bv[4 * q + 3] = b4.w;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < G; j++) bv[j] = 0.0f;
+    }
+    bool any = false;
+#pragma unroll
+    for (int j = 0; j < G; j++) any |= (s[j] != 0) | (bv[j] != 0.0f);
+    if (!any) continue;
+    if (BF) {
+      u16* lh = (u16*)lrow + i0;
+      const uint4 lv = *(const uint4*)lh;
+      const uint32_t w[4] = {lv.x, lv.y, lv.z, lv.w};
+#pragma unroll
+      for (int j = 0; j < G; j++) {
+        if (s[j] == 0 && bv[j] == 0.0f) continue;
+        const u16 hv = (u16)(w[j >> 1] >> ((j & 1) * 16));
+        lh[j] = f2b(logit_adjust_val(b2f(hv), s[j], r, f, p, bv[j]));
+      }
+    } else {
+      float* lf = (float*)lrow + i0;
+      const float4 lv = *(const float4*)lf;
+      const float l[4] = {lv.x, lv.y, lv.z, lv.w};
+#pragma unroll
+      for (int j = 0; j < G; j++) {
+        if (s[j] == 0 && bv[j] == 0.0f) continue;
+        lf[j] = logit_adjust_val(l[j], s[j], r, f, p, bv[j]);
+      }
+    }
+  }
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+k_logit_adjust(void* logits, int V, int lbf16, int* stat,
+               const float* __restrict__ proc,
+               const float* __restrict__ bias,
+               const int* __restrict__ next_token, int count_input) {
+  if (lbf16)
+    logit_adjust_body<true>(logits, V, stat, proc, bias, next_token,
+                            count_input);
+  else
+    logit_adjust_body<false>(logits, V, stat, proc, bias, next_token,
+                             count_input);
+}
+
+extern "C" hipError_t launch_tokstat_mark(void* stat_row, const void* ids,
+                                          int n, int V, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  int blocks = (n + 255) / 256;
+  if (blocks > 64) blocks = 64;
+  hipLaunchKernelGGL(k_tokstat_mark, dim3(blocks), dim3(256), 0, stream,
+                     (int*)stat_row, (const int*)ids, n, V);
+  return hipGetLastError();
+}
+
+// grid: one thread per 16 B group of a row (4 fp32 / 8 bf16 elements),
+// capped like launch_sample's; the loops are grid-stride, so the scalar
+// fallback of a misaligned row is covered by the same grid
+extern "C" hipError_t launch_logit_adjust(void* logits, int V, int lbf16,
+                                          int batch, void* stat,
+                                          const void* proc, const void* bias,
+                                          const void* next_token,
+                                          int count_input,
+                                          hipStream_t stream) {
+  const int groups = V / (lbf16 ? 8 : 4) + 1;
+  int blocks = (groups + 255) / 256;
+  if (blocks > 512) blocks = 512;
+  hipLaunchKernelGGL(k_logit_adjust, dim3(blocks, batch), dim3(256), 0,
+                     stream, logits, V, lbf16, (int*)stat,
+                     (const float*)proc, (const float*)bias,
+                     (const int*)next_token, count_input);
+  return hipGetLastError();
+}
+
+// ====================================================================
 // Prefill GEMM: Y[M,N] = X[M,K] @ W[N,K]^T (+res), bf16 in/out, fp32 acc.
 // MFMA v_mfma_f32_16x16x32_bf16; 128x128 tile, BK=32, 4 waves (2x2),
 // each wave a 64x64 sub-tile (4x4 fragments).  LDS staged, padded rows.

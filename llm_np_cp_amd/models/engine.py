@@ -45,6 +45,9 @@ class GPUModel:
     # runtime (generate(), the server's batch scheduler) routes on this
     device_strategies = frozenset(
         {"greedy", "min_p", "top_k", "top_p", "temperature"})
+    # logit processors the in-graph logit-adjust stage applies (set per
+    # instance: everything at world == 1, nothing under tensor parallel)
+    device_processors = frozenset()
 
     def __init__(self, config: ModelConfig, weights: Dict[str, np.ndarray],
                  dtype: str = "bf16", max_seq: Optional[int] = 4096,
@@ -92,6 +95,18 @@ class GPUModel:
         # exercise the TP code path on 1 GPU (collectives no-op at
         # world=1, partial sums are then exact) — used by tests
         self.tp_branch = self.world > 1 or force_tp_path
+        if self.world == 1:
+            self.device_processors = frozenset(
+                {"logit_bias", "repetition_penalty", "frequency_penalty",
+                 "presence_penalty"})
+        # logit-adjust state (stat / proc / bias rows): allocated by the
+        # first request that brings processors, never otherwise
+        self.p_stat = self.p_proc = self.p_bias = None
+        # host mirror of the device rows: slot -> bias_on, for every
+        # slot whose proc row is not identity (compact_row moves only
+        # what a row actually has; a stale entry is cleared by the next
+        # prefill_row into that slot)
+        self._proc_rows = {}
         if device is None:
             device = f"cuda:{self.rank % max(torch.cuda.device_count(), 1)}"
         self.device = torch.device(device)
@@ -861,16 +876,77 @@ class GPUModel:
         cache.seq_len = len(np.ravel(ids))
         return None, logits, cache, hidden, None
 
+    # ------------------------------------------------------------------
+    # logit processors (penalties / logit_bias): per-row device state
+    # ------------------------------------------------------------------
+    _PROC_IDENTITY = (1.0, 0.0, 0.0, 0.0)
+
+    def _proc_alloc(self):
+        """stat [R, V] i32, proc [R, 4] f32, bias [R, V] f32 with one row
+        per sequence slot (the single-sequence path uses row 0)."""
+        if self.p_stat is not None:
+            return
+        assert self.world == 1, "device logit processors are single-GPU"
+        R, V = self.max_batch, self.config.vocab_size
+        dev = self.device
+        self.p_stat = torch.zeros(R, V, dtype=torch.int32, device=dev)
+        self.p_bias = torch.zeros(R, V, dtype=torch.float32, device=dev)
+        self.p_proc = torch.tensor([self._PROC_IDENTITY] * R,
+                                   dtype=torch.float32, device=dev)
+
+    def setup_processors(self, b: int, prompt_ids, processors):
+        """Start row b's history: zero stat, flag the prompt ids, write
+        the row's penalties and its dense bias.  ``processors`` is the
+        dict of ``sampling.device_sampler_kwargs``; None / missing keys
+        mean identity.  Values are device DATA — captured graphs that
+        carry the adjust stage serve every setting."""
+        self._proc_alloc()
+        pr = processors or {}
+        r = float(pr.get("repetition_penalty", 1.0))
+        f = float(pr.get("frequency_penalty", 0.0))
+        pp = float(pr.get("presence_penalty", 0.0))
+        if not r > 0.0:
+            raise ValueError(f"repetition_penalty must be > 0, got {r}")
+        V = self.config.vocab_size
+        bias = {int(k): float(v)
+                for k, v in (pr.get("logit_bias") or {}).items()
+                if 0 <= int(k) < V}
+        self.p_stat[b].zero_()
+        ids = np.ascontiguousarray(np.asarray(prompt_ids).ravel(),
+                                   dtype=np.int32)
+        if len(ids):
+            ho.tokstat_mark(self.p_stat[b],
+                            torch.from_numpy(ids).to(self.device))
+        if bias:
+            self.p_bias[b].zero_()
+            idx = torch.tensor(list(bias.keys()), dtype=torch.int64,
+                               device=self.device)
+            val = torch.tensor(list(bias.values()), dtype=torch.float32,
+                               device=self.device)
+            self.p_bias[b].index_copy_(0, idx, val)
+        self.p_proc[b].copy_(torch.tensor(
+            [r, f, pp, 1.0 if bias else 0.0], dtype=torch.float32))
+        self._proc_rows[b] = bool(bias)
+
+    def _proc_clear(self, b: int):
+        """Row b carries no processors: identity proc (nothing else of
+        its state is read then)."""
+        if self._proc_rows.pop(b, None) is not None:
+            self.p_proc[b].copy_(torch.tensor(self._PROC_IDENTITY))
+
     def generate_tokens(self, prompt_ids, max_tokens: int,
                         greedy: bool = True, min_p: float = 0.1,
                         eos_id=None, chunk: int = 16, on_ids=None,
                         temperature: float = 1.0, stop_fn=None,
-                        top_k: int = 0, top_p: float = 1.0):
+                        top_k: int = 0, top_p: float = 1.0,
+                        processors=None):
         """Fast generate: device-side hipGraph decode in chunks, host
         sees ids every `chunk` tokens (streaming + EOS stop).  Used by
         runtime.generate() for every strategy in ``device_strategies``
         (``top_k`` > 0 / ``top_p`` < 1 select the device-side filter; 0 /
-        1.0 = off).
+        1.0 = off).  ``processors`` (dict, see ``setup_processors``) switches
+        on the in-graph logit-adjust stage: penalties over the prompt and
+        the generated ids, then logit_bias.
         ``eos_id`` may be an int or a collection of ints (HF configs
         often store a list, e.g. Llama-3.2-Instruct).  ``stop_fn``
         (optional) sees the accumulated ids after each chunk and returns
@@ -889,6 +965,8 @@ class GPUModel:
         t0 = _time.perf_counter()
         with trace_range("prefill"):
             self.prefill(prompt_ids)
+            if processors is not None:
+                self.setup_processors(0, prompt_ids, processors)
         self.last_prefill_time_s = _time.perf_counter() - t0
         out = []
         produced = 0
@@ -899,7 +977,8 @@ class GPUModel:
                 ids = self.decode(n, greedy=greedy, min_p=min_p,
                                   use_graph=True, first_from_logits=first,
                                   temperature=temperature, top_k=top_k,
-                                  top_p=top_p)
+                                  top_p=top_p,
+                                  processors=processors is not None)
                 first = False
                 produced += n
                 stop = False
@@ -971,7 +1050,7 @@ class GPUModel:
 
     def _decode_step(self, greedy: bool, min_p: float,
                      temperature: float = 1.0, top_k: int = 0,
-                     top_p: float = 1.0):
+                     top_p: float = 1.0, proc: bool = False):
         """Fused decode path: 4 kernels/layer (llama) or 5 (gemma) —
         RMSNorm lives inside the GEMV staging pass, RoPE + KV write
         inside the attention kernel.  bf16 weights: the gate+up GEMV
@@ -1129,6 +1208,11 @@ class GPUModel:
                 ho.gemv(self.lm_head, h, self.b_logits_l, **kw)
         if self.tp_branch:
             tpu.all_gather_into(self.b_logits, self.b_logits_l)
+        if proc:
+            # counts next_token (committed by the previous sample) into
+            # the history, then penalties + bias in place
+            ho.logit_adjust(self.b_logits, self.p_stat, self.p_proc,
+                            self.p_bias, self.next_token, True)
         ho.sample(self.b_logits, min_p, greedy, self.seed, self.rng_ctr,
                   self.s_gmax, self.s_pick, self.next_token, self.out_ring,
                   self.nout, self.len_buf, bump_len=True,
@@ -1140,7 +1224,7 @@ class GPUModel:
     # ------------------------------------------------------------------
     def _decode_batch_step(self, B: int, greedy: bool, min_p: float,
                            temperature: float = 1.0, top_k: int = 0,
-                           top_p: float = 1.0):
+                           top_p: float = 1.0, proc: bool = False):
         """One decode step for B lockstep sequences.  fp8 weights with
         B<=8 take the fused MULTI-X GEMV path (one weight stream feeds
         B accumulators — near single-sequence step time); otherwise the
@@ -1157,11 +1241,11 @@ class GPUModel:
         if (self.fp8 and B <= mx_max and not cfg.attention_bias
                 and not self.moe):
             return self._decode_batch_step_mx(B, greedy, min_p, temperature,
-                                              top_k, top_p)
+                                              top_k, top_p, proc)
         if self.fp8 and B <= 16 and not self.moe:
             return self._decode_batch_step_skinny(B, greedy, min_p,
                                                   temperature, top_k,
-                                                  top_p)
+                                                  top_p, proc)
         ho.embed(self.embed, self.bt_next, self.b_h, B, cfg.embed_scale)
         self._layers_forward(B, batch_attn=True)
         ho.rmsnorm(self.b_h[:B], self.g_final, self.b_xn[:B],
@@ -1176,6 +1260,8 @@ class GPUModel:
                     accbuf=self.b_gemm_acc)
         if self.final_softcap:
             ho.softcap(self.bt_logits[:B], self.final_softcap)
+        if proc:
+            self._adjust_rows(B)
         ho.sample(self.bt_logits[:B], min_p, greedy, self.seed,
                   self.rng_ctr, self.bt_gmax, self.bt_pick, self.bt_next,
                   self.bt_ring, self.bt_nout, self.bt_lens, bump_len=True,
@@ -1184,7 +1270,7 @@ class GPUModel:
 
     def _decode_batch_step_mx(self, B: int, greedy: bool, min_p: float,
                               temperature: float = 1.0, top_k: int = 0,
-                              top_p: float = 1.0):
+                              top_p: float = 1.0, proc: bool = False):
         """Fused batched decode (fp8, B<=8): mirrors _decode_step's
         4-5 kernels/layer with multi-x GEMVs over B rows."""
         cfg = self.config
@@ -1257,6 +1343,8 @@ class GPUModel:
                            self.bt_logits, B, H, self.vocab_l,
                            stage=ho.STAGE_NORM, g=self.g_final, eps=eps,
                            softcap=self.final_softcap)
+        if proc:
+            self._adjust_rows(B)
         ho.sample(self.bt_logits[:B], min_p, greedy, self.seed,
                   self.rng_ctr, self.bt_gmax, self.bt_pick, self.bt_next,
                   self.bt_ring, self.bt_nout, self.bt_lens, bump_len=True,
@@ -1265,7 +1353,8 @@ class GPUModel:
 
     def _decode_batch_step_skinny(self, B: int, greedy: bool,
                                   min_p: float, temperature: float = 1.0,
-                                  top_k: int = 0, top_p: float = 1.0):
+                                  top_k: int = 0, top_p: float = 1.0,
+                                  proc: bool = False):
         """Batched decode via (stage+quant, skinny fp8 MFMA GEMM) pairs:
         B = 3..16 lockstep rows, W streamed once per projection."""
         cfg = self.config
@@ -1348,11 +1437,20 @@ class GPUModel:
                            self.bt_logits, B, self.vocab_l,
                            softcap=self.final_softcap,
                            accbuf=self.b_gemm_acc)
+        if proc:
+            self._adjust_rows(B)
         ho.sample(self.bt_logits[:B], min_p, greedy, self.seed,
                   self.rng_ctr, self.bt_gmax, self.bt_pick, self.bt_next,
                   self.bt_ring, self.bt_nout, self.bt_lens, bump_len=True,
                   temperature=temperature, cnt=self.bt_cnt, batch=B,
                   top_k=top_k, top_p=top_p, sel=self.bt_sel)
+
+    def _adjust_rows(self, B: int):
+        """Logit-adjust stage of a lockstep step: every row counts the
+        token its previous sample committed (bt_next), then applies its
+        own penalties / bias to its bt_logits row."""
+        ho.logit_adjust(self.bt_logits[:B], self.p_stat, self.p_proc,
+                        self.p_bias, self.bt_next, True, batch=B)
 
     def prefill_batch(self, prompts) -> None:
         """Prefill B prompts (RAGGED lengths allowed) into per-sequence
@@ -1448,10 +1546,14 @@ class GPUModel:
     # ---- continuous batching primitives (rows join/leave the group) ----
     def prefill_row(self, b: int, ids, greedy: bool = True,
                     min_p: float = 0.1, temperature: float = 1.0,
-                    top_k: int = 0, top_p: float = 1.0):
+                    top_k: int = 0, top_p: float = 1.0, processors=None):
         """Prefill ONE sequence into slot b (other rows untouched) and
         sample its first token — a request JOINING the lockstep group
-        between decode chunks (server continuous batching)."""
+        between decode chunks (server continuous batching).
+        ``processors`` (dict, see ``setup_processors``): the row's own
+        penalties / logit_bias for ``decode_rows(processors=True)``; a
+        row without them gets identity settings, so it may still ride in
+        a processors group."""
         ids = np.asarray(ids, dtype=np.int32).ravel()
         P = len(ids)
         if P == 0:
@@ -1474,6 +1576,14 @@ class GPUModel:
         self._pb = 0
         self.bt_lens[b:b + 1].fill_(P)
         self.bt_nout[b:b + 1].zero_()
+        if processors is not None:
+            self.setup_processors(b, ids, processors)
+            # nothing generated yet: adjust without counting
+            ho.logit_adjust(self.b_logits, self.p_stat[b:b + 1],
+                            self.p_proc[b:b + 1], self.p_bias[b:b + 1],
+                            self.bt_next[b:b + 1], False)
+        else:
+            self._proc_clear(b)
         # first token for this row only (row-sliced sampler state)
         ho.sample(self.b_logits, min_p, greedy, self.seed, self.rng_ctr,
                   self.bt_gmax[b:b + 1], self.bt_pick[b:b + 1],
@@ -1504,21 +1614,39 @@ class GPUModel:
                   self.bt_pick, self.bt_cnt):
             t[dst:dst + 1].copy_(t[src:src + 1])
         self.bt_ring[dst].copy_(self.bt_ring[src])
+        if src in self._proc_rows:
+            # the row's history and settings travel with it (the 4·V-byte
+            # bias row only when it has one); rows without processors
+            # cost nothing here
+            has_bias = self._proc_rows[src]
+            self.p_stat[dst].copy_(self.p_stat[src])
+            self.p_proc[dst].copy_(self.p_proc[src])
+            if has_bias:
+                self.p_bias[dst].copy_(self.p_bias[src])
+            self._proc_rows[dst] = has_bias
+        else:
+            self._proc_clear(dst)
         self._host_lens[dst] = self._host_lens[src]
 
     def decode_rows(self, B: int, n: int, greedy: bool = True,
                     min_p: float = 0.1, temperature: float = 1.0,
                     use_graph: bool = True, top_k: int = 0,
-                    top_p: float = 1.0):
+                    top_p: float = 1.0, processors: bool = False):
         """n lockstep steps for rows [0, B) (each already holding a
         sampled next token from prefill_row / a previous chunk).
+        ``processors``: run the graph variant with the logit-adjust
+        stage (rows set up by ``prefill_row(processors=...)``).
         Returns a list of B arrays: each row's n new token ids."""
         assert 1 <= B <= self.max_batch
+        processors = bool(processors)
+        if processors:
+            self._proc_alloc()
         if max(self._host_lens[:B]) + n > self.max_seq:
             raise ValueError("decode_rows would overflow the KV pool")
         for b in range(B):
             self._host_lens[b] += n
-        key = ("batchc", B, greedy, min_p, temperature, top_k, top_p)
+        key = ("batchc", B, greedy, min_p, temperature, top_k, top_p,
+               processors)
         if not hasattr(self, "_bgraphs"):
             self._bgraphs = {}
         g = self._bgraphs.get(key)
@@ -1529,7 +1657,7 @@ class GPUModel:
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
                 self._decode_batch_step(B, greedy, min_p, temperature,
-                                        top_k, top_p)
+                                        top_k, top_p, processors)
             torch.cuda.current_stream().wait_stream(s)
             torch.cuda.synchronize()
             executed += 1  # the warm-up was a real step
@@ -1537,7 +1665,7 @@ class GPUModel:
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
                     self._decode_batch_step(B, greedy, min_p, temperature,
-                                            top_k, top_p)
+                                            top_k, top_p, processors)
                 self._bgraphs[key] = g
             except Exception as e:
                 self._graph_failed = True
@@ -1550,7 +1678,7 @@ class GPUModel:
         else:
             for _ in range(remaining):
                 self._decode_batch_step(B, greedy, min_p, temperature,
-                                        top_k, top_p)
+                                        top_k, top_p, processors)
         torch.cuda.synchronize()
         comm = tpu.xgmi_comm()
         if comm is not None:
@@ -1573,7 +1701,7 @@ class GPUModel:
 
     def capture_decode_graph(self, greedy: bool = True, min_p: float = 0.1,
                              temperature: float = 1.0, top_k: int = 0,
-                             top_p: float = 1.0):
+                             top_p: float = 1.0, processors: bool = False):
         """Capture one decode step into a hipGraph (fixed shapes: KV pool
         is preallocated and the position is a device scalar — SURVEY §7
         'graph must be shape-stable').
@@ -1586,7 +1714,8 @@ class GPUModel:
         capture failure ``ok`` is False, ``self._graph_failed`` is set
         (no further capture attempts) and the exception is kept in
         ``self._graph_error``."""
-        mode = (greedy, min_p, temperature, top_k, top_p)
+        processors = bool(processors)
+        mode = (greedy, min_p, temperature, top_k, top_p, processors)
         if self._graph_mode == mode:
             return 0, True
         if getattr(self, "_graph_failed", False):
@@ -1595,13 +1724,15 @@ class GPUModel:
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
-            self._decode_step(greedy, min_p, temperature, top_k, top_p)
+            self._decode_step(greedy, min_p, temperature, top_k, top_p,
+                              processors)
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
         try:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                self._decode_step(greedy, min_p, temperature, top_k, top_p)
+                self._decode_step(greedy, min_p, temperature, top_k, top_p,
+                                  processors)
         except Exception as e:
             # the warm-up step above DID run (token committed to
             # out_ring, len_buf advanced) — report it so decode() does
@@ -1623,9 +1754,14 @@ class GPUModel:
     def decode(self, n_tokens: int, greedy: bool = True, min_p: float = 0.1,
                use_graph: bool = True, first_from_logits: bool = True,
                temperature: float = 1.0, top_k: int = 0,
-               top_p: float = 1.0):
+               top_p: float = 1.0, processors: bool = False):
         """Generate n_tokens ids device-side; returns int32 numpy ids.
-        Assumes prefill() ran (len_buf == prompt length, logits ready)."""
+        Assumes prefill() ran (len_buf == prompt length, logits ready).
+        ``processors``: run the logit-adjust stage ahead of every sample
+        with row 0's state (``generate_tokens`` sets it up)."""
+        processors = bool(processors)
+        if processors:
+            self._proc_alloc()
         if getattr(self, "_host_len", 0) + n_tokens > self.max_seq:
             raise ValueError(
                 f"decode would overflow the KV pool: len {self._host_len} "
@@ -1633,6 +1769,9 @@ class GPUModel:
         self._host_len += n_tokens
         if first_from_logits:
             # sample token 0 from the prefill logits
+            if processors:
+                ho.logit_adjust(self.b_logits, self.p_stat, self.p_proc,
+                                self.p_bias, self.next_token, False)
             ho.sample(self.b_logits, min_p, greedy, self.seed, self.rng_ctr,
                       self.s_gmax, self.s_pick, self.next_token,
                       self.out_ring, self.nout, self.len_buf,
@@ -1644,7 +1783,7 @@ class GPUModel:
             # capture_decode_graph reports the warm-up step it executed
             # even when capture fails, so n_steps stays exact either way
             taken, ok = self.capture_decode_graph(greedy, min_p, temperature,
-                                                  top_k, top_p)
+                                                  top_k, top_p, processors)
             n_steps -= taken
             if not ok:
                 use_graph = False
@@ -1653,7 +1792,8 @@ class GPUModel:
                 self._graph.replay()
         else:
             for _ in range(n_steps):
-                self._decode_step(greedy, min_p, temperature, top_k, top_p)
+                self._decode_step(greedy, min_p, temperature, top_k, top_p,
+                                  processors)
         torch.cuda.synchronize()
         comm = tpu.xgmi_comm()
         if comm is not None:

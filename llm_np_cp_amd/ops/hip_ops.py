@@ -64,6 +64,11 @@ _SIGS = {
                          [ctypes.c_void_p] * 8 +
                          [ctypes.c_int, ctypes.c_int, ctypes.c_float,
                           ctypes.c_void_p, ctypes.c_void_p],
+    "launch_logit_adjust": [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                            ctypes.c_int] + [ctypes.c_void_p] * 4 +
+                           [ctypes.c_int, ctypes.c_void_p],
+    "launch_tokstat_mark": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                            ctypes.c_int, ctypes.c_void_p],
     "launch_gemm_bf16": [ctypes.c_void_p] * 5 + [ctypes.c_int] * 3 +
                         [ctypes.c_void_p],
     "launch_prefetch": [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p,
@@ -402,6 +407,60 @@ def sample(logits: torch.Tensor, min_p: float, greedy: bool, seed: int,
         _ptr(ctr), _ptr(gmax), _ptr(pick), _ptr(cnt),
         _ptr(next_token), _ptr(out_ring), _ptr(nout), _ptr(len_ptr),
         1 if bump_len else 0, _stream()), "sample")
+
+
+# stat word layout of the logit-adjust stage (csrc/llm_ops.hip): bit 30 =
+# "id occurs in the prompt", low 30 bits = times the id was generated
+TOKSTAT_PROMPT = 1 << 30
+TOKSTAT_COUNT = TOKSTAT_PROMPT - 1
+
+
+def tokstat_mark(stat_row: torch.Tensor, ids: torch.Tensor):
+    """Flag the prompt ``ids`` (int32, device) in one freshly zeroed
+    ``stat`` row (int32 [V]); ids outside [0, V) are ignored."""
+    if stat_row.dtype != torch.int32 or stat_row.dim() != 1 \
+            or not stat_row.is_contiguous():
+        raise ValueError("stat_row must be a contiguous int32 [V] row")
+    if ids.dtype != torch.int32 or not ids.is_contiguous():
+        raise ValueError("ids must be contiguous int32")
+    _check(lib().launch_tokstat_mark(
+        _ptr(stat_row), _ptr(ids), ids.numel(), stat_row.numel(),
+        _stream()), "tokstat_mark")
+
+
+def logit_adjust(logits: torch.Tensor, stat: torch.Tensor,
+                 proc: torch.Tensor, bias: torch.Tensor,
+                 next_token: torch.Tensor, count_input: bool,
+                 batch: int = 1):
+    """Penalties + logit_bias, in place on ``batch`` logits rows (fp32 or
+    bf16, [batch, V] contiguous) ahead of ``sample``.  Per row b:
+    ``stat[b]`` (int32 [V]: TOKSTAT_PROMPT flag | generated count),
+    ``proc[b]`` (fp32 {repetition, frequency, presence, bias_on}) and
+    ``bias[b]`` (fp32 [V], read when bias_on != 0).  ``count_input``:
+    first count ``next_token[b]`` — the token the previous ``sample``
+    committed — into ``stat[b]``; off for the first sample after a
+    prefill.  A row with identity ``proc`` is left alone entirely."""
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"logits must be fp32 or bf16, got {logits.dtype}")
+    V = logits.shape[-1]
+    if not logits.is_contiguous() or logits.numel() < batch * V:
+        raise ValueError("logits must hold `batch` contiguous rows")
+    if stat.dtype != torch.int32 or not stat.is_contiguous() \
+            or stat.shape[-1] != V or stat.numel() < batch * V:
+        raise ValueError("stat must be contiguous int32 [>=batch, V]")
+    if bias.dtype != torch.float32 or not bias.is_contiguous() \
+            or bias.shape[-1] != V or bias.numel() < batch * V:
+        raise ValueError("bias must be contiguous fp32 [>=batch, V]")
+    if proc.dtype != torch.float32 or not proc.is_contiguous() \
+            or proc.shape[-1] != 4 or proc.numel() < batch * 4:
+        raise ValueError("proc must be contiguous fp32 [>=batch, 4]")
+    if next_token.dtype != torch.int32 or next_token.numel() < batch:
+        raise ValueError("next_token must be int32 with `batch` entries")
+    lbf16 = 1 if logits.dtype == torch.bfloat16 else 0
+    _check(lib().launch_logit_adjust(
+        _ptr(logits), V, lbf16, batch, _ptr(stat), _ptr(proc), _ptr(bias),
+        _ptr(next_token), 1 if count_input else 0, _stream()),
+        "logit_adjust")
 
 
 def gemm(X: torch.Tensor, W: torch.Tensor, Y: torch.Tensor,

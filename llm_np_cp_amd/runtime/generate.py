@@ -23,7 +23,8 @@ from typing import Callable, List, Optional
 
 import numpy as np
 
-from .sampling import SamplingParams, device_sampler_kwargs, sample_token
+from .sampling import (SamplingParams, active_processors,
+                       device_sampler_kwargs, sample_token)
 
 
 @dataclass
@@ -140,8 +141,9 @@ def generate(prompt: str, tokenizer, model, max_tokens: int = 200,
     Seeds: the GPU fast path's device sampler derives its stream from
     the ENGINE seed + a device counter (baked into the captured graph),
     so ``params.seed`` is honored on the logits-visible paths (CPU
-    oracle; logprobs / logit_bias requests; strategies the engine does
-    not list in ``device_strategies``) but not by the in-graph device
+    oracle; logprobs requests; strategies or logit processors the
+    engine does not list in ``device_strategies`` /
+    ``device_processors``) but not by the in-graph device
     sampler — on an engine that advertises them that now includes
     top-k / top-p / temperature, as it always did min-p."""
     params = params or SamplingParams()
@@ -176,7 +178,11 @@ def generate(prompt: str, tokenizer, model, max_tokens: int = 200,
     # its device sampler implements, cached mode) — same sampler
     # semantics, device RNG.  Engines that do not advertise
     # device_strategies get greedy / min-p only, with the original kwargs.
-    if (use_cache and logprobs is None and not params.logit_bias
+    # Penalties / logit_bias ride along when the engine advertises every
+    # active one in device_processors (the in-graph logit-adjust stage).
+    if (use_cache and logprobs is None
+            and active_processors(params) <= frozenset(
+                getattr(model, "device_processors", ()))
             and hasattr(model, "generate_tokens")
             and params.strategy in getattr(model, "device_strategies",
                                            ("greedy", "min_p"))):
@@ -218,7 +224,7 @@ def generate(prompt: str, tokenizer, model, max_tokens: int = 200,
     t1 = time.perf_counter()
     for _ in range(max_tokens):
         row = np.asarray(logits[-1], dtype=np.float32)
-        next_id = sample_token(row, params, rng)
+        next_id = sample_token(row, params, rng, prompt_ids, out_ids)
         out_ids.append(next_id)
         if lp_entries is not None:
             lp_entries.append(_logprob_entry(row, next_id, logprobs,

@@ -27,6 +27,69 @@ class SamplingParams:
     # OpenAI-style per-token logit offsets {token_id: bias}; applied to
     # the raw logits before temperature/filtering (+-100 ~ ban/force)
     logit_bias: Optional[dict] = None
+    # history-aware processors, applied to the raw logits in this order
+    # and BEFORE logit_bias (see apply_logit_processors):
+    # HF-style repetition penalty over prompt + generated ids (> 0;
+    # 1.0 = off), then OpenAI-style frequency / presence penalties over
+    # the generated ids only (0.0 = off)
+    repetition_penalty: float = 1.0
+    frequency_penalty: float = 0.0
+    presence_penalty: float = 0.0
+
+
+def active_processors(params: "SamplingParams") -> frozenset:
+    """Names of the logit processors ``params`` actually switches on."""
+    act = set()
+    if params.repetition_penalty != 1.0:
+        act.add("repetition_penalty")
+    if params.frequency_penalty != 0.0:
+        act.add("frequency_penalty")
+    if params.presence_penalty != 0.0:
+        act.add("presence_penalty")
+    if params.logit_bias:
+        act.add("logit_bias")
+    return frozenset(act)
+
+
+def has_processors(params: "SamplingParams") -> bool:
+    """True when any penalty is off its identity value or a logit_bias
+    is present — i.e. the logits row is edited before the sampler."""
+    return bool(active_processors(params))
+
+
+def apply_logit_processors(logits: np.ndarray, params: "SamplingParams",
+                           prompt_ids=(), output_ids=()) -> np.ndarray:
+    """Raw logits row -> the row the sampler reads.  Fixed order:
+
+    1. repetition_penalty r over every id in prompt_ids or output_ids:
+       ``l/r`` if ``l > 0`` else ``l*r`` (HF rule);
+    2. with c[i] the count of i in output_ids only:
+       ``l[i] -= frequency_penalty*c[i] + presence_penalty*(c[i] > 0)``;
+    3. ``l[i] += logit_bias[i]``.
+
+    fp32 arithmetic on a copy; without processors the input comes back
+    as is."""
+    if not has_processors(params):
+        return logits
+    logits = np.array(logits, dtype=np.float32, copy=True)
+    V = len(logits)
+    r = float(params.repetition_penalty)
+    f = float(params.frequency_penalty)
+    p = float(params.presence_penalty)
+    if r <= 0.0:
+        raise ValueError(f"repetition_penalty must be > 0, got {r}")
+    out = np.asarray(list(output_ids), dtype=np.int64).reshape(-1)
+    out = out[(out >= 0) & (out < V)]
+    if r != 1.0:
+        pr = np.asarray(list(prompt_ids), dtype=np.int64).reshape(-1)
+        pr = pr[(pr >= 0) & (pr < V)]
+        seen = np.unique(np.concatenate([pr, out]))
+        l = logits[seen]
+        logits[seen] = np.where(l > 0, l / np.float32(r), l * np.float32(r))
+    if (f != 0.0 or p != 0.0) and len(out):
+        c = np.bincount(out, minlength=V).astype(np.float32)
+        logits -= np.float32(f) * c + np.float32(p) * (c > 0)
+    return _apply_bias(logits, params)
 
 
 def _apply_bias(logits: np.ndarray, params: "SamplingParams") -> np.ndarray:
@@ -47,15 +110,17 @@ def _softmax(x: np.ndarray) -> np.ndarray:
     return e / e.sum()
 
 
-def filter_probs(logits: np.ndarray, params: SamplingParams) -> np.ndarray:
+def filter_probs(logits: np.ndarray, params: SamplingParams,
+                 prompt_ids=(), output_ids=()) -> np.ndarray:
     """The sampling DISTRIBUTION the strategy defines: temperature-scaled
     softmax with the strategy's support filter applied, renormalized.
     (fp64, sums to 1.)  ``sample_token`` draws from this; speculative
     sampling (runtime/speculative.py) needs the vector itself to compute
-    accept ratios p(x)/q(x) and the residual distribution.  logit_bias
-    applies first, so every consumer (host sampler, speculative
-    accept/reject) sees the same biased distribution."""
-    logits = _apply_bias(logits, params)
+    accept ratios p(x)/q(x) and the residual distribution.  The logit
+    processors (penalties over ``prompt_ids`` / ``output_ids``, then
+    logit_bias) apply first, so every consumer (host sampler,
+    speculative accept/reject) sees the same adjusted distribution."""
+    logits = apply_logit_processors(logits, params, prompt_ids, output_ids)
     if params.strategy == "greedy":
         p = np.zeros(len(logits), dtype=np.float64)
         p[int(np.argmax(logits))] = 1.0
@@ -90,11 +155,21 @@ def device_sampler_kwargs(params: SamplingParams) -> dict:
     distribution ``filter_probs`` defines for ``params``.  greedy and
     min_p yield exactly ``greedy`` / ``min_p`` / ``temperature``, so
     engines that predate the device-side filters keep working; the filter
-    keys appear only for the strategies that need them.  (``seed`` and
-    ``logit_bias`` have no device counterpart — callers keep such
-    requests on the host path.)"""
+    keys appear only for the strategies that need them.  ``processors``
+    (the penalties and logit_bias of the device logit-adjust stage)
+    appears only when ``has_processors(params)``; callers send such a
+    request to the device only when the engine lists every active one
+    in ``device_processors``.  (``seed`` has no device counterpart —
+    callers keep such requests on the host path.)"""
     kw = dict(greedy=params.strategy == "greedy", min_p=params.min_p,
               temperature=params.temperature)
+    if has_processors(params):
+        kw["processors"] = dict(
+            repetition_penalty=float(params.repetition_penalty),
+            frequency_penalty=float(params.frequency_penalty),
+            presence_penalty=float(params.presence_penalty),
+            logit_bias=dict(params.logit_bias) if params.logit_bias
+            else None)
     if params.strategy in ("greedy", "min_p"):
         return kw
     kw["min_p"] = 0.0  # empty min-p cut: the whole vocabulary stays
@@ -110,11 +185,14 @@ def device_sampler_kwargs(params: SamplingParams) -> dict:
 
 
 def sample_token(logits: np.ndarray, params: SamplingParams,
-                 rng: Optional[np.random.Generator] = None) -> int:
-    """logits: (vocab,) fp32. Returns a token id (int)."""
+                 rng: Optional[np.random.Generator] = None,
+                 prompt_ids=(), output_ids=()) -> int:
+    """logits: (vocab,) fp32. Returns a token id (int).  ``prompt_ids``
+    / ``output_ids`` feed the penalties (apply_logit_processors)."""
     if params.strategy == "greedy":
-        return int(np.argmax(_apply_bias(logits, params)))
+        return int(np.argmax(apply_logit_processors(
+            logits, params, prompt_ids, output_ids)))
     if rng is None:
         rng = np.random.default_rng(params.seed)
-    probs = filter_probs(logits, params)
+    probs = filter_probs(logits, params, prompt_ids, output_ids)
     return int(rng.choice(len(probs), p=probs))

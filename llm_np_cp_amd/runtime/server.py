@@ -15,8 +15,9 @@ and queued compatible requests JOIN mid-flight (``prefill_row`` into a
 free slot) — continuous batching, not fixed groups.  Requests with
 sampling strategies the engine's device sampler does not implement
 (``device_strategies``; top_k/top_p/temperature on engines without the
-selection stage) or a non-batch engine fall back to single-sequence
-generate().
+selection stage), with penalties / ``logit_bias`` on an engine that does
+not list them in ``device_processors``, or a non-batch engine fall back
+to single-sequence generate().
 
     python -m llm_np_cp_amd.runtime.server --model llama-3.2-1b \
         --port 8080 --max-batch 8
@@ -34,7 +35,7 @@ from dataclasses import dataclass, field
 from typing import Optional
 
 try:  # pydantic model must live at module scope (ForwardRef resolution)
-    from typing import Literal
+    from typing import Dict, Literal
 
     from pydantic import BaseModel, Field
 
@@ -54,7 +55,13 @@ try:  # pydantic model must live at module scope (ForwardRef resolution)
         stop: Optional[list] = None   # stop strings (OpenAI semantics)
         logprobs: Optional[int] = None  # top-N per-token logprobs
         n: int = Field(1, ge=1, le=16)  # independent samples
-        logit_bias: Optional[dict] = None  # {token_id: bias}
+        # {token_id: bias}; keys / values that are not numbers get a 422
+        logit_bias: Optional[Dict[int, float]] = None
+        # OpenAI-style penalties over the generated tokens, HF-style
+        # repetition penalty over prompt + generated tokens
+        presence_penalty: float = Field(0.0, ge=-2, le=2)
+        frequency_penalty: float = Field(0.0, ge=-2, le=2)
+        repetition_penalty: float = Field(1.0, gt=0)
         echo: bool = False        # prepend the prompt to the text
 
     class ChatMessage(BaseModel):
@@ -75,11 +82,51 @@ try:  # pydantic model must live at module scope (ForwardRef resolution)
         stop: Optional[list] = None
         logprobs: Optional[int] = None
         n: int = Field(1, ge=1, le=16)
-        logit_bias: Optional[dict] = None
+        logit_bias: Optional[Dict[int, float]] = None
+        # OpenAI-style penalties over the generated tokens, HF-style
+        # repetition penalty over prompt + generated tokens
+        presence_penalty: float = Field(0.0, ge=-2, le=2)
+        frequency_penalty: float = Field(0.0, ge=-2, le=2)
+        repetition_penalty: float = Field(1.0, gt=0)
 except ImportError:  # pragma: no cover - serving is optional
     CompletionRequest = None
     ChatMessage = None
     ChatCompletionRequest = None
+
+
+def _sampling_params(req, seed=None):
+    """Request -> SamplingParams (request objects that predate a field
+    get its default)."""
+    from .sampling import SamplingParams
+
+    bias = getattr(req, "logit_bias", None)
+    return SamplingParams(
+        strategy=req.strategy, min_p=req.min_p,
+        temperature=req.temperature, seed=seed,
+        top_k=getattr(req, "top_k", 50),
+        top_p=getattr(req, "top_p", 0.9),
+        logit_bias={int(k): float(v) for k, v in bias.items()}
+        if bias else None,
+        repetition_penalty=getattr(req, "repetition_penalty", 1.0),
+        frequency_penalty=getattr(req, "frequency_penalty", 0.0),
+        presence_penalty=getattr(req, "presence_penalty", 0.0))
+
+
+def _req_processors(req) -> frozenset:
+    """Names of the logit processors a request switches on.  Runs on the
+    scheduler thread for every queued request, so it only LOOKS at the
+    fields: converting them (which can raise on a malformed logit_bias)
+    is left to the code that serves the request, inside its try."""
+    act = set()
+    if getattr(req, "logit_bias", None):
+        act.add("logit_bias")
+    if getattr(req, "repetition_penalty", 1.0) != 1.0:
+        act.add("repetition_penalty")
+    if getattr(req, "frequency_penalty", 0.0) != 0.0:
+        act.add("frequency_penalty")
+    if getattr(req, "presence_penalty", 0.0) != 0.0:
+        act.add("presence_penalty")
+    return frozenset(act)
 
 
 class ClientDisconnected(Exception):
@@ -103,8 +150,12 @@ class BatchScheduler:
 
     def __init__(self, generate_one, run_group, max_batch: int,
                  window_s: float = 0.004,
-                 device_strategies=("greedy", "min_p")):
+                 device_strategies=("greedy", "min_p"),
+                 device_processors=()):
         self.generate_one = generate_one
+        # logit processors (penalties / logit_bias) run_group's engine
+        # applies on device, per row — such requests may join a group
+        self.device_processors = frozenset(device_processors)
         # strategies run_group's engine samples on device (lockstep group)
         self.device_strategies = frozenset(device_strategies)
         self.run_group = run_group  # (pendings, poll_fn) -> resolves them
@@ -136,7 +187,10 @@ class BatchScheduler:
         return (req.strategy, round(req.min_p, 6),
                 round(req.temperature, 6), req.stop_on_eos,
                 getattr(req, "top_k", 50),
-                round(getattr(req, "top_p", 0.9), 6))
+                round(getattr(req, "top_p", 0.9), 6),
+                # processor VALUES are per-row device data: all requests
+                # with any processor share one group and one graph
+                bool(_req_processors(req)))
 
     def _batchable(self, req) -> bool:
         # streaming and stop-string requests take the generate_one
@@ -147,7 +201,7 @@ class BatchScheduler:
                 and not getattr(req, "stream", False)
                 and not getattr(req, "stop", None)
                 and getattr(req, "logprobs", None) is None
-                and not getattr(req, "logit_bias", None)
+                and _req_processors(req) <= self.device_processors
                 and not getattr(req, "echo", False)
                 and getattr(req, "n", 1) == 1)
 
@@ -316,14 +370,7 @@ def build_app(model_name: str = "llama-3.2-1b", backend: str = "auto",
         for idx in range(n):
             seed = (req.seed + idx) if (req.seed is not None and n > 1) \
                 else req.seed
-            bias = getattr(req, "logit_bias", None)
-            params = L.SamplingParams(
-                strategy=req.strategy, min_p=req.min_p,
-                temperature=req.temperature, seed=seed,
-                top_k=getattr(req, "top_k", 50),
-                top_p=getattr(req, "top_p", 0.9),
-                logit_bias={int(k): float(vv) for k, vv in bias.items()}
-                if bias else None)
+            params = _sampling_params(req, seed)
             out = L.generate(req.prompt, tok, model,
                              max_tokens=req.max_tokens, params=params,
                              stream=False, stop_on_eos=req.stop_on_eos,
@@ -383,12 +430,27 @@ def build_app(model_name: str = "llama-3.2-1b", backend: str = "auto",
             temperature=r0.temperature,
             top_k=getattr(r0, "top_k", 50),
             top_p=getattr(r0, "top_p", 0.9)))
+        # a processors group (_key): each row brings its OWN penalties /
+        # bias (device data), the decode graph just carries the stage
+        with_proc = bool(_req_processors(r0))
+        dkw = dict(skw, processors=True) if with_proc else skw
         rows: list = []  # slot -> _Row
 
         def admit(p):
             slot = len(rows)
             t_p = time.time()
-            model.prefill_row(slot, tok.encode(p.req.prompt), **skw)
+            pkw = skw
+            if with_proc:
+                try:
+                    pkw = dict(skw, processors=device_sampler_kwargs(
+                        _sampling_params(p.req))["processors"])
+                except (TypeError, ValueError) as e:
+                    # a malformed logit_bias fails this request alone
+                    stats["requests"] += 1
+                    p.error = e
+                    p.done.set()
+                    return
+            model.prefill_row(slot, tok.encode(p.req.prompt), **pkw)
             p.prefill_s = time.time() - t_p
             rows.append(_Row(p))
             stats["requests"] += 1
@@ -424,7 +486,7 @@ def build_app(model_name: str = "llama-3.2-1b", backend: str = "auto",
                 rows[longest] = rows[B - 1]
                 rows.pop()
                 continue
-            out = model.decode_rows(B, chunk, **skw)
+            out = model.decode_rows(B, chunk, **dkw)
             # the first sampled token (from prefill_row) precedes chunk 1
             for b in range(B):
                 row = rows[b]
@@ -464,7 +526,9 @@ def build_app(model_name: str = "llama-3.2-1b", backend: str = "auto",
                            window_s=batch_window_ms / 1e3,
                            device_strategies=getattr(
                                model, "device_strategies",
-                               ("greedy", "min_p")))
+                               ("greedy", "min_p")),
+                           device_processors=getattr(
+                               model, "device_processors", ()))
     app = FastAPI(title="llm_np_cp_amd", version=L.__version__)
 
     @app.get("/v1/models")
@@ -565,7 +629,10 @@ def build_app(model_name: str = "llama-3.2-1b", backend: str = "auto",
             strategy=req.strategy, seed=req.seed,
             stop_on_eos=req.stop_on_eos, stream=req.stream,
             stop=req.stop, logprobs=req.logprobs, n=req.n,
-            logit_bias=req.logit_bias)
+            logit_bias=req.logit_bias,
+            presence_penalty=req.presence_penalty,
+            frequency_penalty=req.frequency_penalty,
+            repetition_penalty=req.repetition_penalty)
         if req.stream:
             return _sse(creq, lambda piece: {
                 "object": "chat.completion.chunk", "model": model_name,

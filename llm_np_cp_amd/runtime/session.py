@@ -21,7 +21,7 @@ from typing import List, Optional
 import numpy as np
 
 from .generate import GenerateResult
-from .sampling import SamplingParams, sample_token
+from .sampling import SamplingParams, has_processors, sample_token
 
 
 class ChatSession:
@@ -88,7 +88,7 @@ class ChatSession:
         t1 = time.perf_counter()
         greedy_or_minp = self.params.strategy in ("greedy", "min_p")
         if (hasattr(self.model, "decode") and greedy_or_minp
-                and not self.params.logit_bias):
+                and not has_processors(self.params)):
             # GPU engine: continue with the device-side hipGraph loop
             # (the prefill logits above are already in b_logits)
             produced = 0
@@ -121,10 +121,14 @@ class ChatSession:
                     self.cache.seq_len)
             self.cache.seq_len = len(self.token_ids) + len(out)
         else:
+            # host loop (also every session with penalties / logit_bias):
+            # the transcript so far is the "prompt", this turn's reply
+            # the "output" of the logit processors
             for _ in range(max_tokens):
                 nid = sample_token(np.asarray(logits[-1],
                                               dtype=np.float32),
-                                   self.params, self._rng)
+                                   self.params, self._rng,
+                                   self.token_ids, out)
                 out.append(nid)
                 hit_eos = stop_on_eos and nid in self.eos_set
                 # forward EVERY sampled token (the eos included) so the

@@ -125,6 +125,13 @@ def generate_speculative(prompt: str, tokenizer, draft, target,
         raise ValueError("k must be >= 1")
     if params is None:
         params = SamplingParams(strategy="greedy")
+    if (params.repetition_penalty != 1.0 or params.frequency_penalty != 0.0
+            or params.presence_penalty != 0.0):
+        # the accept/reject rule would need the per-position history of
+        # every drafted token; logit_bias (history-free) keeps working
+        raise ValueError(
+            "repetition/frequency/presence penalties are not supported "
+            "under speculative decoding")
     rng = np.random.default_rng(params.seed)
 
     def _pick(logits_row: np.ndarray) -> int:
