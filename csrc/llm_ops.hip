@@ -3114,6 +3114,295 @@ extern "C" hipError_t launch_logit_adjust(void* logits, int V, int lbf16,
 }
 
 // ====================================================================
+// Logprobs: log-softmax of the RAW logits row (after the lm_head, before
+// k_logit_adjust) reduced to {chosen logprob, top-N ids + logprobs} per
+// token, inside the decode step.  Per-row device data, so rows with
+// different N (and rows without logprobs) share one graph:
+//   lp_cfg [rows]        i32  -1 = row off (nothing of it is touched),
+//                             0..LOGPROBS_MAX_TOP = the row's top-N
+//   part   [rows, stride] u64 scan scratch: [0] ticket, [1, 1+nblk) one
+//                             (m, s) pair per block, then nblk x 20 packed
+//                             (fkey, id) words; all zero between launches
+//   stage  [rows, 48]    f32  [0] M = row max, [1..20] top logits,
+//                             [21] log S (S = sum exp(l - M)), [24..43] top
+//                             ids; lse = M + log S is never formed: the
+//                             logprob is (l - M) - log S, so a uniformly
+//                             shifted row loses nothing to the size of M
+//   raw    [rows, V]     f32  optional copy of the row (steps that adjust
+//                             the logits in place before sampling)
+//   lp_val [rows, LP_RING, 21] f32  {chosen, top_0 .. top_19} logprobs
+//   lp_idx [rows, LP_RING, 20] i32  top ids
+// k_logprob_scan: block x owns logits [x*2048, x*2048+2048), 8 per thread,
+// kept in registers: local max m, s = sum exp(l - m), and its top-N as
+// packed (fkey(l), id) words (ties -> smaller id).  Packed words are
+// unique, so "not yet taken" is "below the previous winner": N rounds of a
+// wave arg-max per wave, then wave 0 merges the 4 wave lists.  The
+// last-arriving block (ticket) merges the partials in a fixed order over
+// the BLOCK INDEX — never the arrival order — so two launches on the same
+// row give the same bits: M = max_b m_b, S = sum_b s_b * exp(m_b - M).
+// k_logprob_commit (after the sampler): record (nout-1) mod LP_RING gets
+// (l - M) - log S for the sampled token and the row's top-N.
+// ====================================================================
+#define LOGPROBS_MAX_TOP 20
+#define LP_RING 256
+#define LP_SLICE 2048       // logits per scan block
+#define LP_EPT 8            // = LP_SLICE / 256
+#define LP_MERGE_EPT 16     // merge candidates per thread of the last block
+#define LP_MAX_BLOCKS 204   // 204 * 20 <= 256 * LP_MERGE_EPT
+#define LP_STAGE_WORDS 48
+#define LP_STAGE_LOGS 21
+#define LP_STAGE_IDS 24
+
+// lane r (r < N) returns the r-th largest of the wave's packed words
+// (K per lane, 0 = empty slot; 0 is below every real word); 0 when the
+// wave holds fewer than r+1
+template <int K>
+DEVINL uint64_t lp_wave_topn(const uint64_t (&k)[K], int N) {
+  const int lane = threadIdx.x & 63;
+  uint64_t prev = ~0ull, mine = 0ull;
+  for (int r = 0; r < N; r++) {
+    uint64_t best = 0ull;
+#pragma unroll
+    for (int j = 0; j < K; j++)
+      if (k[j] < prev && k[j] > best) best = k[j];
+#pragma unroll
+    for (int w = 1; w < 64; w <<= 1) {
+      uint64_t o = __shfl_xor((unsigned long long)best, w);
+      if (o > best) best = o;
+    }
+    if (lane == r) mine = best;
+    prev = best;
+  }
+  return mine;
+}
+
+DEVINL float lp_wave_max(float v) {
+#pragma unroll
+  for (int w = 1; w < 64; w <<= 1) v = fmaxf(v, __shfl_xor(v, w));
+  return v;
+}
+
+// 4 wave lists (N words each, in wl) -> wave 0's lanes r < N hold the
+// block's r-th largest word
+DEVINL uint64_t lp_merge_waves(const unsigned long long* wl, int N) {
+  const int lane = threadIdx.x & 63;
+  uint64_t c[2];
+  c[0] = lane < 4 * N ? wl[lane] : 0ull;
+  c[1] = lane + 64 < 4 * N ? wl[lane + 64] : 0ull;
+  return lp_wave_topn<2>(c, N);
+}
+
+template <bool BF>
+DEVINL void logprob_scan_body(const void* logits, int V, const int* lp_cfg,
+                              unsigned long long* part, long part_stride,
+                              float* stage, float* raw) {
+  const int b = blockIdx.y;
+  int N = lp_cfg[b];
+  if (N < 0) return;  // row off
+  if (N > LOGPROBS_MAX_TOP) N = LOGPROBS_MAX_TOP;
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int nblk = gridDim.x;
+  const size_t row0 = (size_t)b * V;
+  part += (size_t)b * part_stride;
+  unsigned long long* pms = part + 1;
+  unsigned long long* ptop = part + 1 + nblk;
+  stage += (size_t)b * LP_STAGE_WORDS;
+  __shared__ float wm[4], wsum[4];
+  __shared__ unsigned long long wl[4 * LOGPROBS_MAX_TOP];
+  __shared__ int lastflag;
+
+  // scalar loads: bf16 rows with odd V start 2-byte aligned
+  float v[LP_EPT];
+  uint64_t k[LP_EPT];
+  float m = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < LP_EPT; j++) {
+    const int i = blockIdx.x * LP_SLICE + j * 256 + t;
+    v[j] = -INFINITY;
+    k[j] = 0ull;
+    if (i < V) {
+      const float x = BF ? b2f(((const u16*)logits)[row0 + i])
+                         : ((const float*)logits)[row0 + i];
+      v[j] = x;
+      k[j] = pack_ki(fkey(x), i);
+      m = fmaxf(m, x);
+      if (raw) raw[row0 + i] = x;
+    }
+  }
+  m = lp_wave_max(m);
+  if (lane == 0) wm[wv] = m;
+  __syncthreads();
+  m = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
+  float s = 0.0f;
+  if (m > -INFINITY) {
+#pragma unroll
+    for (int j = 0; j < LP_EPT; j++) s += expf(v[j] - m);
+  }
+  s = wave_reduce_sum(s);
+  if (lane == 0) wsum[wv] = s;
+  const uint64_t mine = lp_wave_topn<LP_EPT>(k, N);
+  if (lane < N) wl[wv * N + lane] = mine;
+  __syncthreads();
+  // wave 0 writes the whole partial, so ONE wave's release fence orders
+  // it ahead of the ticket (as in k_sample_select)
+  if (wv == 0) {
+    const uint64_t top = lp_merge_waves(wl, N);
+    if (lane < N) ptop[blockIdx.x * LOGPROBS_MAX_TOP + lane] = top;
+    if (lane == 0) {
+      const float bs = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+      pms[blockIdx.x] = ((unsigned long long)__float_as_uint(bs) << 32) |
+                        __float_as_uint(m);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    if (lane == 0) {
+      unsigned long long tk = __hip_atomic_fetch_add(
+          &part[0], 1ull, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+      lastflag = (tk == (unsigned long long)nblk - 1);
+    }
+  }
+  __syncthreads();
+  if (!lastflag) return;
+  // last arriver: every block's partial is in; merge by block index,
+  // re-arm ticket and scratch
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  if (wv == 0) {
+    float M = -INFINITY;
+    for (int i = lane; i < nblk; i += 64) {
+      const unsigned long long u = __hip_atomic_load(
+          &pms[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      M = fmaxf(M, __uint_as_float((uint32_t)u));
+    }
+    M = lp_wave_max(M);
+    float S = 0.0f;
+    for (int i = lane; i < nblk; i += 64) {
+      const unsigned long long u = __hip_atomic_load(
+          &pms[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const float mi = __uint_as_float((uint32_t)u);
+      const float si = __uint_as_float((uint32_t)(u >> 32));
+      if (mi > -INFINITY) S += si * expf(mi - M);
+      pms[i] = 0ull;
+    }
+    S = wave_reduce_sum(S);
+    if (lane == 0) {
+      stage[0] = M;
+      stage[LP_STAGE_LOGS] = M > -INFINITY ? logf(S) : 0.0f;
+      part[0] = 0ull;
+    }
+  }
+  if (N == 0) return;
+  const int total = nblk * N;
+  uint64_t c[LP_MERGE_EPT];
+#pragma unroll
+  for (int j = 0; j < LP_MERGE_EPT; j++) {
+    const int ci = j * 256 + t;
+    c[j] = 0ull;
+    if (ci < total) {
+      const int blk = ci / N;
+      unsigned long long* p = ptop + blk * LOGPROBS_MAX_TOP + (ci - blk * N);
+      c[j] = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      *p = 0ull;
+    }
+  }
+  const uint64_t mine2 = lp_wave_topn<LP_MERGE_EPT>(c, N);
+  if (lane < N) wl[wv * N + lane] = mine2;
+  __syncthreads();
+  if (wv == 0) {
+    const uint64_t top = lp_merge_waves(wl, N);
+    if (lane < N) {
+      // fewer than N logits in the row: id -1, logit -inf
+      stage[1 + lane] =
+          top ? fkey_inv((uint32_t)(top >> 32)) : -INFINITY;
+      ((int*)stage)[LP_STAGE_IDS + lane] = top ? unpack_idx(top) : -1;
+    }
+  }
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+k_logprob_scan(const void* __restrict__ logits, int V, int lbf16,
+               const int* __restrict__ lp_cfg, unsigned long long* part,
+               long part_stride, float* __restrict__ stage,
+               float* __restrict__ raw) {
+  if (lbf16)
+    logprob_scan_body<true>(logits, V, lp_cfg, part, part_stride, stage, raw);
+  else
+    logprob_scan_body<false>(logits, V, lp_cfg, part, part_stride, stage,
+                             raw);
+}
+
+DEVINL float lp_sub(float l, float M, float logS) {
+  return l == -INFINITY ? -INFINITY : (l - M) - logS;
+}
+
+// one wave per row, after the sampler committed next_token / nout
+extern "C" __global__ void __launch_bounds__(64)
+k_logprob_commit(const void* __restrict__ logits, int V, int lbf16,
+                 const int* __restrict__ lp_cfg,
+                 const float* __restrict__ stage,
+                 const float* __restrict__ raw,
+                 const int* __restrict__ next_token,
+                 const int* __restrict__ nout, float* __restrict__ lp_val,
+                 int* __restrict__ lp_idx) {
+  const int b = blockIdx.y;
+  int N = lp_cfg[b];
+  if (N < 0) return;
+  if (N > LOGPROBS_MAX_TOP) N = LOGPROBS_MAX_TOP;
+  const int t = threadIdx.x;
+  stage += (size_t)b * LP_STAGE_WORDS;
+  const int slot = (nout[b] - 1) & (LP_RING - 1);
+  const size_t rec = (size_t)b * LP_RING + slot;
+  float* val = lp_val + rec * (1 + LOGPROBS_MAX_TOP);
+  int* idx = lp_idx + rec * LOGPROBS_MAX_TOP;
+  const float M = stage[0], logS = stage[LP_STAGE_LOGS];
+  if (t == 0) {
+    int tok = next_token[b];
+    if (tok < 0 || tok >= V) tok = 0;
+    const size_t at = (size_t)b * V + tok;
+    const float l = raw ? raw[at]
+                        : lbf16 ? b2f(((const u16*)logits)[at])
+                                : ((const float*)logits)[at];
+    val[0] = lp_sub(l, M, logS);
+  }
+  if (t < N) {
+    val[1 + t] = lp_sub(stage[1 + t], M, logS);
+    idx[t] = ((const int*)stage)[LP_STAGE_IDS + t];
+  }
+}
+
+// part_stride: u64 words per scratch row, >= 1 + 21 * ceil(V / 2048)
+extern "C" hipError_t launch_logprob_scan(const void* logits, int V,
+                                          int lbf16, int batch,
+                                          const void* lp_cfg, void* part,
+                                          long part_stride, void* stage,
+                                          void* raw, hipStream_t stream) {
+  const int nblk = (V + LP_SLICE - 1) / LP_SLICE;
+  if (V <= 0 || nblk > LP_MAX_BLOCKS ||
+      part_stride < 1 + (long)nblk * (1 + LOGPROBS_MAX_TOP))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_logprob_scan, dim3(nblk, batch), dim3(256), 0, stream,
+                     logits, V, lbf16, (const int*)lp_cfg,
+                     (unsigned long long*)part, part_stride, (float*)stage,
+                     (float*)raw);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t launch_logprob_commit(const void* logits, int V,
+                                            int lbf16, int batch,
+                                            const void* lp_cfg,
+                                            const void* stage,
+                                            const void* raw,
+                                            const void* next_token,
+                                            const void* nout, void* lp_val,
+                                            void* lp_idx,
+                                            hipStream_t stream) {
+  hipLaunchKernelGGL(k_logprob_commit, dim3(1, batch), dim3(64), 0, stream,
+                     logits, V, lbf16, (const int*)lp_cfg,
+                     (const float*)stage, (const float*)raw,
+                     (const int*)next_token, (const int*)nout,
+                     (float*)lp_val, (int*)lp_idx);
+  return hipGetLastError();
+}
+
+// ====================================================================
 // Prefill GEMM: Y[M,N] = X[M,K] @ W[N,K]^T (+res), bf16 in/out, fp32 acc.
 // MFMA v_mfma_f32_16x16x32_bf16; 128x128 tile, BK=32, 4 waves (2x2),
 // each wave a 64x64 sub-tile (4x4 fragments).  LDS staged, padded rows.

@@ -48,6 +48,9 @@ class GPUModel:
     # logit processors the in-graph logit-adjust stage applies (set per
     # instance: everything at world == 1, nothing under tensor parallel)
     device_processors = frozenset()
+    # largest top-N the in-graph logprob stage reports per token (set per
+    # instance: LOGPROBS_MAX_TOP at world == 1, 0 under tensor parallel)
+    device_logprobs = 0
 
     def __init__(self, config: ModelConfig, weights: Dict[str, np.ndarray],
                  dtype: str = "bf16", max_seq: Optional[int] = 4096,
@@ -107,6 +110,16 @@ class GPUModel:
         # what a row actually has; a stale entry is cleared by the next
         # prefill_row into that slot)
         self._proc_rows = {}
+        if self.world == 1:
+            self.device_logprobs = ho.LOGPROBS_MAX_TOP
+        # logprob state (cfg / stage / scan scratch / record rings, raw
+        # snapshot): allocated by the first request that asks for
+        # logprobs.  _lp_rows: slot -> top-N of every row that is on
+        self.lp_cfg = self.lp_stage = self.lp_part = None
+        self.lp_val = self.lp_idx = self.lp_raw = None
+        self._lp_rows = {}
+        self._lp_batch = False  # records follow bt_nout (else nout)
+        self.last_logprobs = None
         if device is None:
             device = f"cuda:{self.rank % max(torch.cuda.device_count(), 1)}"
         self.device = torch.device(device)
@@ -934,19 +947,109 @@ class GPUModel:
         if self._proc_rows.pop(b, None) is not None:
             self.p_proc[b].copy_(torch.tensor(self._PROC_IDENTITY))
 
+    # ------------------------------------------------------------------
+    # logprobs: per-row device state of the in-graph logprob stage
+    # ------------------------------------------------------------------
+    def _lp_alloc(self, raw: bool = False):
+        """lp_cfg [R] i32 (-1 = off), stage [R, 48] f32, scan scratch
+        [R, words(V)] i64, record rings lp_val [R, LP_RING, 21] f32 /
+        lp_idx [R, LP_RING, 20] i32 with one row per sequence slot (the
+        single-sequence path uses row 0).  ``raw``: also the fp32 logits
+        snapshot [R, V], needed only by steps that adjust the logits."""
+        assert self.world == 1, "device logprobs are single-GPU"
+        R, V = self.max_batch, self.config.vocab_size
+        dev = self.device
+        if self.lp_cfg is None:
+            W = ho.LOGPROBS_MAX_TOP
+            self.lp_cfg = torch.full((R,), -1, dtype=torch.int32, device=dev)
+            self.lp_stage = torch.zeros(R, ho.LP_STAGE_WORDS,
+                                        dtype=torch.float32, device=dev)
+            self.lp_part = torch.zeros(R, ho.logprob_part_words(V),
+                                       dtype=torch.int64, device=dev)
+            self.lp_val = torch.zeros(R, ho.LP_RING, 1 + W,
+                                      dtype=torch.float32, device=dev)
+            self.lp_idx = torch.zeros(R, ho.LP_RING, W, dtype=torch.int32,
+                                      device=dev)
+        if raw and self.lp_raw is None:
+            self.lp_raw = torch.zeros(R, V, dtype=torch.float32, device=dev)
+
+    def setup_logprobs(self, b: int, n):
+        """Row b reports the chosen token's logprob and its top-``n``
+        (0..device_logprobs) per token from now on; ``n`` None switches
+        the row off.  N is device DATA — captured graphs that carry the
+        logprob stage serve every N."""
+        if n is None:
+            self._lp_clear(b)
+            return
+        n = int(n)
+        if not 0 <= n <= self.device_logprobs:
+            raise ValueError(f"logprobs must be within 0.."
+                             f"{self.device_logprobs}, got {n}")
+        self._lp_alloc()
+        ho.logprob_set_cfg(self.lp_cfg, b, n)
+        self._lp_rows[b] = n
+
+    def _lp_clear(self, b: int):
+        """Row b carries no logprobs: cfg -1 (the kernels then touch
+        nothing of the row)."""
+        if self._lp_rows.pop(b, None) is not None:
+            ho.logprob_set_cfg(self.lp_cfg, b, -1)
+
+    def _lp_scan(self, logits, sl: slice, proc: bool):
+        """Logprob scan of the RAW rows ``logits`` (state rows ``sl``);
+        steps that adjust the logits next also snapshot them."""
+        raw = self.lp_raw[sl] if proc else None
+        ho.logprob_scan(logits, self.lp_cfg[sl], self.lp_part[sl],
+                        self.lp_stage[sl], raw=raw, batch=sl.stop - sl.start)
+
+    def _lp_commit(self, logits, sl: slice, proc: bool, next_token, nout):
+        raw = self.lp_raw[sl] if proc else None
+        ho.logprob_commit(logits, self.lp_cfg[sl], self.lp_stage[sl],
+                          next_token, nout, self.lp_val[sl], self.lp_idx[sl],
+                          raw=raw, batch=sl.stop - sl.start)
+
+    def logprob_records(self, n: int, row: int = 0):
+        """Records of the last ``n`` tokens committed on ``row``:
+        ``(chosen_lp [n] f32, top_ids [n, N] i32, top_lp [n, N] f32)``
+        numpy arrays, N the row's own top-N; ``top_lp`` is sorted
+        descending (ties by ascending id).  The ring keeps LP_RING
+        tokens, so drain at least that often."""
+        if row not in self._lp_rows:
+            raise ValueError(f"row {row} has no logprobs set up")
+        if not 0 <= n <= ho.LP_RING:
+            raise ValueError(f"the logprob ring keeps {ho.LP_RING} records, "
+                             f"asked for {n}")
+        N = self._lp_rows[row]
+        torch.cuda.synchronize()
+        cnt = self.bt_nout if self._lp_batch else self.nout
+        end = int(cnt[row].item())
+        if n > end:
+            raise ValueError(f"row {row} committed {end} tokens, asked for "
+                             f"{n} records")
+        slots = (np.arange(end - n, end) % ho.LP_RING).astype(np.int64)
+        val = self.lp_val[row].cpu().numpy()[slots]
+        idx = self.lp_idx[row].cpu().numpy()[slots]
+        return (val[:, 0].copy(), idx[:, :N].copy(), val[:, 1:1 + N].copy())
+
     def generate_tokens(self, prompt_ids, max_tokens: int,
                         greedy: bool = True, min_p: float = 0.1,
                         eos_id=None, chunk: int = 16, on_ids=None,
                         temperature: float = 1.0, stop_fn=None,
                         top_k: int = 0, top_p: float = 1.0,
-                        processors=None):
+                        processors=None, logprobs=None):
         """Fast generate: device-side hipGraph decode in chunks, host
         sees ids every `chunk` tokens (streaming + EOS stop).  Used by
         runtime.generate() for every strategy in ``device_strategies``
         (``top_k`` > 0 / ``top_p`` < 1 select the device-side filter; 0 /
         1.0 = off).  ``processors`` (dict, see ``setup_processors``) switches
         on the in-graph logit-adjust stage: penalties over the prompt and
-        the generated ids, then logit_bias.
+        the generated ids, then logit_bias.  ``logprobs`` (int N within
+        0..``device_logprobs``, or None) switches on the in-graph logprob
+        stage: afterwards ``self.last_logprobs`` holds ``(chosen_lp [n],
+        top_ids [n, N], top_lp [n, N])`` numpy arrays of the RAW model
+        distribution (before processors / temperature), one row per
+        returned id (a caller that truncates the ids on a stop string
+        truncates them alike); None when logprobs were not asked for.
         ``eos_id`` may be an int or a collection of ints (HF configs
         often store a list, e.g. Llama-3.2-Instruct).  ``stop_fn``
         (optional) sees the accumulated ids after each chunk and returns
@@ -967,7 +1070,13 @@ class GPUModel:
             self.prefill(prompt_ids)
             if processors is not None:
                 self.setup_processors(0, prompt_ids, processors)
+            if logprobs is not None:
+                self.setup_logprobs(0, logprobs)
+                chunk = min(chunk, ho.LP_RING)  # drained per chunk
         self.last_prefill_time_s = _time.perf_counter() - t0
+        self.last_logprobs = None
+        lpkw = {"logprobs": True} if logprobs is not None else {}
+        recs = []
         out = []
         produced = 0
         first = True
@@ -978,7 +1087,7 @@ class GPUModel:
                                   use_graph=True, first_from_logits=first,
                                   temperature=temperature, top_k=top_k,
                                   top_p=top_p,
-                                  processors=processors is not None)
+                                  processors=processors is not None, **lpkw)
                 first = False
                 produced += n
                 stop = False
@@ -988,12 +1097,24 @@ class GPUModel:
                     take = take[:hit[0] + 1]
                     stop = True
                 out.extend(take)
+                if logprobs is not None:
+                    rec = self.logprob_records(len(ids))
+                    recs.append(tuple(a[:len(take)] for a in rec))
                 if on_ids:
                     on_ids(take)
                 if stop:
                     break
                 if stop_fn is not None and stop_fn(out):
                     break
+        if logprobs is not None:
+            N = int(logprobs)
+            self.last_logprobs = (
+                np.concatenate([r[0] for r in recs]) if recs
+                else np.zeros(0, np.float32),
+                np.concatenate([r[1] for r in recs]) if recs
+                else np.zeros((0, N), np.int32),
+                np.concatenate([r[2] for r in recs]) if recs
+                else np.zeros((0, N), np.float32))
         return out
 
     # ------------------------------------------------------------------
@@ -1050,7 +1171,8 @@ class GPUModel:
 
     def _decode_step(self, greedy: bool, min_p: float,
                      temperature: float = 1.0, top_k: int = 0,
-                     top_p: float = 1.0, proc: bool = False):
+                     top_p: float = 1.0, proc: bool = False,
+                     logprobs: bool = False):
         """Fused decode path: 4 kernels/layer (llama) or 5 (gemma) —
         RMSNorm lives inside the GEMV staging pass, RoPE + KV write
         inside the attention kernel.  bf16 weights: the gate+up GEMV
@@ -1208,6 +1330,9 @@ class GPUModel:
                 ho.gemv(self.lm_head, h, self.b_logits_l, **kw)
         if self.tp_branch:
             tpu.all_gather_into(self.b_logits, self.b_logits_l)
+        if logprobs:
+            # max / log-sum + top-N of the RAW row (ahead of any adjustment)
+            self._lp_scan(self.b_logits, slice(0, 1), proc)
         if proc:
             # counts next_token (committed by the previous sample) into
             # the history, then penalties + bias in place
@@ -1218,13 +1343,17 @@ class GPUModel:
                   self.nout, self.len_buf, bump_len=True,
                   temperature=temperature, cnt=self.s_cnt,
                   top_k=top_k, top_p=top_p, sel=self.s_sel)
+        if logprobs:
+            self._lp_commit(self.b_logits, slice(0, 1), proc,
+                            self.next_token, self.nout)
 
     # ------------------------------------------------------------------
     # lockstep batched decode (throughput mode; beyond-parity capability)
     # ------------------------------------------------------------------
     def _decode_batch_step(self, B: int, greedy: bool, min_p: float,
                            temperature: float = 1.0, top_k: int = 0,
-                           top_p: float = 1.0, proc: bool = False):
+                           top_p: float = 1.0, proc: bool = False,
+                           logprobs: bool = False):
         """One decode step for B lockstep sequences.  fp8 weights with
         B<=8 take the fused MULTI-X GEMV path (one weight stream feeds
         B accumulators — near single-sequence step time); otherwise the
@@ -1241,11 +1370,11 @@ class GPUModel:
         if (self.fp8 and B <= mx_max and not cfg.attention_bias
                 and not self.moe):
             return self._decode_batch_step_mx(B, greedy, min_p, temperature,
-                                              top_k, top_p, proc)
+                                              top_k, top_p, proc, logprobs)
         if self.fp8 and B <= 16 and not self.moe:
             return self._decode_batch_step_skinny(B, greedy, min_p,
                                                   temperature, top_k,
-                                                  top_p, proc)
+                                                  top_p, proc, logprobs)
         ho.embed(self.embed, self.bt_next, self.b_h, B, cfg.embed_scale)
         self._layers_forward(B, batch_attn=True)
         ho.rmsnorm(self.b_h[:B], self.g_final, self.b_xn[:B],
@@ -1260,6 +1389,8 @@ class GPUModel:
                     accbuf=self.b_gemm_acc)
         if self.final_softcap:
             ho.softcap(self.bt_logits[:B], self.final_softcap)
+        if logprobs:
+            self._lp_scan(self.bt_logits[:B], slice(0, B), proc)
         if proc:
             self._adjust_rows(B)
         ho.sample(self.bt_logits[:B], min_p, greedy, self.seed,
@@ -1267,10 +1398,14 @@ class GPUModel:
                   self.bt_ring, self.bt_nout, self.bt_lens, bump_len=True,
                   temperature=temperature, cnt=self.bt_cnt, batch=B,
                   top_k=top_k, top_p=top_p, sel=self.bt_sel)
+        if logprobs:
+            self._lp_commit(self.bt_logits[:B], slice(0, B), proc,
+                            self.bt_next, self.bt_nout)
 
     def _decode_batch_step_mx(self, B: int, greedy: bool, min_p: float,
                               temperature: float = 1.0, top_k: int = 0,
-                              top_p: float = 1.0, proc: bool = False):
+                              top_p: float = 1.0, proc: bool = False,
+                              logprobs: bool = False):
         """Fused batched decode (fp8, B<=8): mirrors _decode_step's
         4-5 kernels/layer with multi-x GEMVs over B rows."""
         cfg = self.config
@@ -1343,6 +1478,8 @@ class GPUModel:
                            self.bt_logits, B, H, self.vocab_l,
                            stage=ho.STAGE_NORM, g=self.g_final, eps=eps,
                            softcap=self.final_softcap)
+        if logprobs:
+            self._lp_scan(self.bt_logits[:B], slice(0, B), proc)
         if proc:
             self._adjust_rows(B)
         ho.sample(self.bt_logits[:B], min_p, greedy, self.seed,
@@ -1350,11 +1487,15 @@ class GPUModel:
                   self.bt_ring, self.bt_nout, self.bt_lens, bump_len=True,
                   temperature=temperature, cnt=self.bt_cnt, batch=B,
                   top_k=top_k, top_p=top_p, sel=self.bt_sel)
+        if logprobs:
+            self._lp_commit(self.bt_logits[:B], slice(0, B), proc,
+                            self.bt_next, self.bt_nout)
 
     def _decode_batch_step_skinny(self, B: int, greedy: bool,
                                   min_p: float, temperature: float = 1.0,
                                   top_k: int = 0, top_p: float = 1.0,
-                                  proc: bool = False):
+                                  proc: bool = False,
+                                  logprobs: bool = False):
         """Batched decode via (stage+quant, skinny fp8 MFMA GEMM) pairs:
         B = 3..16 lockstep rows, W streamed once per projection."""
         cfg = self.config
@@ -1437,6 +1578,8 @@ class GPUModel:
                            self.bt_logits, B, self.vocab_l,
                            softcap=self.final_softcap,
                            accbuf=self.b_gemm_acc)
+        if logprobs:
+            self._lp_scan(self.bt_logits[:B], slice(0, B), proc)
         if proc:
             self._adjust_rows(B)
         ho.sample(self.bt_logits[:B], min_p, greedy, self.seed,
@@ -1444,6 +1587,9 @@ class GPUModel:
                   self.bt_ring, self.bt_nout, self.bt_lens, bump_len=True,
                   temperature=temperature, cnt=self.bt_cnt, batch=B,
                   top_k=top_k, top_p=top_p, sel=self.bt_sel)
+        if logprobs:
+            self._lp_commit(self.bt_logits[:B], slice(0, B), proc,
+                            self.bt_next, self.bt_nout)
 
     def _adjust_rows(self, B: int):
         """Logit-adjust stage of a lockstep step: every row counts the
@@ -1492,31 +1638,50 @@ class GPUModel:
                      min_p: float = 0.1, temperature: float = 1.0,
                      use_graph: bool = True,
                      first_from_logits: bool = True,
-                     top_k: int = 0, top_p: float = 1.0) -> np.ndarray:
+                     top_k: int = 0, top_p: float = 1.0,
+                     logprobs: bool = False) -> np.ndarray:
         """Decode n_tokens for every prefilled sequence; returns int32
         ids of shape (B, n_tokens).  ``first_from_logits=False``
-        continues a previous decode_batch (chunked serving)."""
+        continues a previous decode_batch (chunked serving).
+        ``logprobs``: run the logprob stage for the rows switched on with
+        ``setup_logprobs`` (read back with ``logprob_records``)."""
         B = self._batch_n
+        logprobs = bool(logprobs)
+        if logprobs:
+            if n_tokens > ho.LP_RING:
+                raise ValueError(f"logprobs: at most {ho.LP_RING} tokens "
+                                 f"per call, got {n_tokens}")
+            self._lp_alloc()
+            self._lp_batch = True
+        # (proc, logprobs) of the step functions; nothing when off
+        extra = (False, True) if logprobs else ()
         if max(self._host_lens) + n_tokens > self.max_seq:
             raise ValueError("decode_batch would overflow the KV pool")
         self._host_lens = [p + n_tokens for p in self._host_lens]
         if first_from_logits:
             # first tokens from the prefill logits (fp32, batch rows)
+            if logprobs:
+                self._lp_scan(self.bt_logits32[:B], slice(0, B), False)
             ho.sample(self.bt_logits32[:B], min_p, greedy, self.seed,
                       self.rng_ctr, self.bt_gmax, self.bt_pick,
                       self.bt_next, self.bt_ring, self.bt_nout,
                       self.bt_lens, bump_len=False,
                       temperature=temperature, cnt=self.bt_cnt, batch=B,
                       top_k=top_k, top_p=top_p, sel=self.bt_sel)
+            if logprobs:
+                self._lp_commit(self.bt_logits32[:B], slice(0, B), False,
+                                self.bt_next, self.bt_nout)
         n_steps = n_tokens - (1 if first_from_logits else 0)
         key = ("batch", B, greedy, min_p, temperature, top_k, top_p)
+        if logprobs:
+            key += ("logprobs",)
         if use_graph and n_steps > 0 and self._graph_mode != key \
                 and not getattr(self, "_graph_failed", False):
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
                 self._decode_batch_step(B, greedy, min_p, temperature,
-                                        top_k, top_p)
+                                        top_k, top_p, *extra)
             torch.cuda.current_stream().wait_stream(s)
             torch.cuda.synchronize()
             n_steps -= 1
@@ -1524,7 +1689,7 @@ class GPUModel:
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
                     self._decode_batch_step(B, greedy, min_p, temperature,
-                                            top_k, top_p)
+                                            top_k, top_p, *extra)
                 self._graph = g
                 self._graph_mode = key
             except Exception as e:
@@ -1537,7 +1702,7 @@ class GPUModel:
         else:
             for _ in range(n_steps):
                 self._decode_batch_step(B, greedy, min_p, temperature,
-                                        top_k, top_p)
+                                        top_k, top_p, *extra)
         torch.cuda.synchronize()
         n = int(self.bt_nout[0].item())
         out = self.bt_ring[:B, :n].cpu().numpy()
@@ -1546,10 +1711,15 @@ class GPUModel:
     # ---- continuous batching primitives (rows join/leave the group) ----
     def prefill_row(self, b: int, ids, greedy: bool = True,
                     min_p: float = 0.1, temperature: float = 1.0,
-                    top_k: int = 0, top_p: float = 1.0, processors=None):
+                    top_k: int = 0, top_p: float = 1.0, processors=None,
+                    logprobs=None):
         """Prefill ONE sequence into slot b (other rows untouched) and
         sample its first token — a request JOINING the lockstep group
         between decode chunks (server continuous batching).
+        ``logprobs`` (int N within 0..``device_logprobs``, or None): the
+        row's own top-N for ``decode_rows(logprobs=True)``; its first
+        token's record is written here.  A row without it is switched
+        off, so it may still ride in a logprobs group.
         ``processors`` (dict, see ``setup_processors``): the row's own
         penalties / logit_bias for ``decode_rows(processors=True)``; a
         row without them gets identity settings, so it may still ride in
@@ -1576,6 +1746,15 @@ class GPUModel:
         self._pb = 0
         self.bt_lens[b:b + 1].fill_(P)
         self.bt_nout[b:b + 1].zero_()
+        rb = slice(b, b + 1)
+        if logprobs is not None:
+            if processors is not None:
+                self._lp_alloc(raw=True)
+            self.setup_logprobs(b, logprobs)
+            self._lp_batch = True
+            self._lp_scan(self.b_logits, rb, processors is not None)
+        else:
+            self._lp_clear(b)
         if processors is not None:
             self.setup_processors(b, ids, processors)
             # nothing generated yet: adjust without counting
@@ -1592,6 +1771,9 @@ class GPUModel:
                   bump_len=False, temperature=temperature,
                   cnt=self.bt_cnt[b:b + 1], batch=1,
                   top_k=top_k, top_p=top_p, sel=self.bt_sel[b:b + 1])
+        if logprobs is not None:
+            self._lp_commit(self.b_logits, rb, processors is not None,
+                            self.bt_next[rb], self.bt_nout[rb])
         if not hasattr(self, "_host_lens") or self._host_lens is None:
             self._host_lens = [0] * self.max_batch
         while len(self._host_lens) < self.max_batch:
@@ -1626,27 +1808,48 @@ class GPUModel:
             self._proc_rows[dst] = has_bias
         else:
             self._proc_clear(dst)
+        if src in self._lp_rows:
+            # cfg, stage and the record ring travel with the row; the
+            # scan scratch is all zero between steps and the raw
+            # snapshot lives within one step, so neither moves
+            for t in (self.lp_cfg, self.lp_stage, self.lp_val, self.lp_idx):
+                t[dst:dst + 1].copy_(t[src:src + 1])
+            self._lp_rows[dst] = self._lp_rows[src]
+        else:
+            self._lp_clear(dst)
         self._host_lens[dst] = self._host_lens[src]
 
     def decode_rows(self, B: int, n: int, greedy: bool = True,
                     min_p: float = 0.1, temperature: float = 1.0,
                     use_graph: bool = True, top_k: int = 0,
-                    top_p: float = 1.0, processors: bool = False):
+                    top_p: float = 1.0, processors: bool = False,
+                    logprobs: bool = False):
         """n lockstep steps for rows [0, B) (each already holding a
         sampled next token from prefill_row / a previous chunk).
         ``processors``: run the graph variant with the logit-adjust
         stage (rows set up by ``prefill_row(processors=...)``).
+        ``logprobs``: run the graph variant with the logprob stage (rows
+        set up by ``prefill_row(logprobs=N)``; at most LP_RING steps per
+        call — drain with ``logprob_records`` in between).
         Returns a list of B arrays: each row's n new token ids."""
         assert 1 <= B <= self.max_batch
         processors = bool(processors)
         if processors:
             self._proc_alloc()
+        logprobs = bool(logprobs)
+        if logprobs:
+            if n > ho.LP_RING:
+                raise ValueError(f"logprobs: at most {ho.LP_RING} tokens "
+                                 f"per call, got {n}")
+            self._lp_alloc(raw=processors)
+            self._lp_batch = True
+        lpx = (True,) if logprobs else ()
         if max(self._host_lens[:B]) + n > self.max_seq:
             raise ValueError("decode_rows would overflow the KV pool")
         for b in range(B):
             self._host_lens[b] += n
         key = ("batchc", B, greedy, min_p, temperature, top_k, top_p,
-               processors)
+               processors) + (("logprobs",) if logprobs else ())
         if not hasattr(self, "_bgraphs"):
             self._bgraphs = {}
         g = self._bgraphs.get(key)
@@ -1657,7 +1860,7 @@ class GPUModel:
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
                 self._decode_batch_step(B, greedy, min_p, temperature,
-                                        top_k, top_p, processors)
+                                        top_k, top_p, processors, *lpx)
             torch.cuda.current_stream().wait_stream(s)
             torch.cuda.synchronize()
             executed += 1  # the warm-up was a real step
@@ -1665,7 +1868,7 @@ class GPUModel:
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
                     self._decode_batch_step(B, greedy, min_p, temperature,
-                                            top_k, top_p, processors)
+                                            top_k, top_p, processors, *lpx)
                 self._bgraphs[key] = g
             except Exception as e:
                 self._graph_failed = True
@@ -1678,7 +1881,7 @@ class GPUModel:
         else:
             for _ in range(remaining):
                 self._decode_batch_step(B, greedy, min_p, temperature,
-                                        top_k, top_p, processors)
+                                        top_k, top_p, processors, *lpx)
         torch.cuda.synchronize()
         comm = tpu.xgmi_comm()
         if comm is not None:
@@ -1701,10 +1904,13 @@ class GPUModel:
 
     def capture_decode_graph(self, greedy: bool = True, min_p: float = 0.1,
                              temperature: float = 1.0, top_k: int = 0,
-                             top_p: float = 1.0, processors: bool = False):
+                             top_p: float = 1.0, processors: bool = False,
+                             logprobs: bool = False):
         """Capture one decode step into a hipGraph (fixed shapes: KV pool
         is preallocated and the position is a device scalar — SURVEY §7
-        'graph must be shape-stable').
+        'graph must be shape-stable').  ``logprobs``: the step carries the
+        logprob stage (scan ahead of the adjust stage, commit after the
+        sampler).
 
         NOTE: the warm-up executes ONE REAL decode step (advances the
         sequence by one token).  Returns ``(steps_taken, ok)``:
@@ -1716,6 +1922,11 @@ class GPUModel:
         ``self._graph_error``."""
         processors = bool(processors)
         mode = (greedy, min_p, temperature, top_k, top_p, processors)
+        lpx = (True,) if logprobs else ()
+        if logprobs:
+            # the logprob stage is part of the key; N is not (device data)
+            mode += ("logprobs",)
+            self._lp_alloc(raw=processors)
         if self._graph_mode == mode:
             return 0, True
         if getattr(self, "_graph_failed", False):
@@ -1725,14 +1936,14 @@ class GPUModel:
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             self._decode_step(greedy, min_p, temperature, top_k, top_p,
-                              processors)
+                              processors, *lpx)
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
         try:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 self._decode_step(greedy, min_p, temperature, top_k, top_p,
-                                  processors)
+                                  processors, *lpx)
         except Exception as e:
             # the warm-up step above DID run (token committed to
             # out_ring, len_buf advanced) — report it so decode() does
@@ -1754,14 +1965,27 @@ class GPUModel:
     def decode(self, n_tokens: int, greedy: bool = True, min_p: float = 0.1,
                use_graph: bool = True, first_from_logits: bool = True,
                temperature: float = 1.0, top_k: int = 0,
-               top_p: float = 1.0, processors: bool = False):
+               top_p: float = 1.0, processors: bool = False,
+               logprobs: bool = False):
         """Generate n_tokens ids device-side; returns int32 numpy ids.
         Assumes prefill() ran (len_buf == prompt length, logits ready).
         ``processors``: run the logit-adjust stage ahead of every sample
-        with row 0's state (``generate_tokens`` sets it up)."""
+        with row 0's state (``generate_tokens`` sets it up).
+        ``logprobs``: run the logprob stage around every sample with row
+        0's top-N (``setup_logprobs(0, N)``; ``generate_tokens`` does it);
+        read the records with ``logprob_records`` — at most LP_RING
+        tokens per call."""
         processors = bool(processors)
         if processors:
             self._proc_alloc()
+        logprobs = bool(logprobs)
+        if logprobs:
+            if n_tokens > ho.LP_RING:
+                raise ValueError(f"logprobs: at most {ho.LP_RING} tokens "
+                                 f"per call, got {n_tokens}")
+            self._lp_alloc(raw=processors)
+            self._lp_batch = False
+        lpx = (True,) if logprobs else ()
         if getattr(self, "_host_len", 0) + n_tokens > self.max_seq:
             raise ValueError(
                 f"decode would overflow the KV pool: len {self._host_len} "
@@ -1769,6 +1993,8 @@ class GPUModel:
         self._host_len += n_tokens
         if first_from_logits:
             # sample token 0 from the prefill logits
+            if logprobs:
+                self._lp_scan(self.b_logits, slice(0, 1), processors)
             if processors:
                 ho.logit_adjust(self.b_logits, self.p_stat, self.p_proc,
                                 self.p_bias, self.next_token, False)
@@ -1778,12 +2004,16 @@ class GPUModel:
                       bump_len=False, temperature=temperature,
                       cnt=self.s_cnt, top_k=top_k, top_p=top_p,
                       sel=self.s_sel)
+            if logprobs:
+                self._lp_commit(self.b_logits, slice(0, 1), processors,
+                                self.next_token, self.nout)
         n_steps = n_tokens - (1 if first_from_logits else 0)
         if use_graph and n_steps > 0:
             # capture_decode_graph reports the warm-up step it executed
             # even when capture fails, so n_steps stays exact either way
             taken, ok = self.capture_decode_graph(greedy, min_p, temperature,
-                                                  top_k, top_p, processors)
+                                                  top_k, top_p, processors,
+                                                  *lpx)
             n_steps -= taken
             if not ok:
                 use_graph = False
@@ -1793,7 +2023,7 @@ class GPUModel:
         else:
             for _ in range(n_steps):
                 self._decode_step(greedy, min_p, temperature, top_k, top_p,
-                                  processors)
+                                  processors, *lpx)
         torch.cuda.synchronize()
         comm = tpu.xgmi_comm()
         if comm is not None:

@@ -69,6 +69,11 @@ _SIGS = {
                            [ctypes.c_int, ctypes.c_void_p],
     "launch_tokstat_mark": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                             ctypes.c_int, ctypes.c_void_p],
+    "launch_logprob_scan": [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                            ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                            ctypes.c_long] + [ctypes.c_void_p] * 3,
+    "launch_logprob_commit": [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                              ctypes.c_int] + [ctypes.c_void_p] * 8,
     "launch_gemm_bf16": [ctypes.c_void_p] * 5 + [ctypes.c_int] * 3 +
                         [ctypes.c_void_p],
     "launch_prefetch": [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p,
@@ -461,6 +466,122 @@ def logit_adjust(logits: torch.Tensor, stat: torch.Tensor,
         _ptr(logits), V, lbf16, batch, _ptr(stat), _ptr(proc), _ptr(bias),
         _ptr(next_token), 1 if count_input else 0, _stream()),
         "logit_adjust")
+
+
+# logprob stage (csrc/llm_ops.hip): record width, ring length, scan slice
+LOGPROBS_MAX_TOP = 20
+LP_RING = 256
+LP_SLICE = 2048
+LP_MAX_BLOCKS = 204
+LP_STAGE_WORDS = 48   # fp32 words per row: [0] row max M, [1..20] top
+LP_STAGE_LOGS = 21    # logits, [21] log sum exp(l - M), top ids at
+LP_STAGE_IDS = 24     # [24..43] (int32 bits)
+
+
+def logprob_part_words(V: int) -> int:
+    """int64 words of scan scratch one row of V logits needs: ticket +
+    per block one (m, s) word and LOGPROBS_MAX_TOP packed (key, id) words."""
+    nblk = (V + LP_SLICE - 1) // LP_SLICE
+    if V <= 0 or nblk > LP_MAX_BLOCKS:
+        raise ValueError(f"logprob scan supports 1 <= V <= "
+                         f"{LP_MAX_BLOCKS * LP_SLICE}, got {V}")
+    return 1 + nblk * (1 + LOGPROBS_MAX_TOP)
+
+
+def logprob_set_cfg(lp_cfg: torch.Tensor, row: int, n):
+    """Write row ``row`` of ``lp_cfg``: ``n`` None / -1 switches the row
+    off, 0..LOGPROBS_MAX_TOP is its top-N.  The values are device data the
+    kernels cannot report on, so the range is checked here."""
+    n = -1 if n is None else int(n)
+    if not -1 <= n <= LOGPROBS_MAX_TOP:
+        raise ValueError(f"logprobs top-N must be within 0.."
+                         f"{LOGPROBS_MAX_TOP} (or None / -1 = off), got {n}")
+    if lp_cfg.dtype != torch.int32 or not 0 <= row < lp_cfg.numel():
+        raise ValueError("lp_cfg must be int32 with an entry for `row`")
+    lp_cfg[row:row + 1].fill_(n)
+
+
+def _logprob_common(logits, lp_cfg, stage, raw, batch):
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"logits must be fp32 or bf16, got {logits.dtype}")
+    V = logits.shape[-1]
+    if batch < 1 or not logits.is_contiguous() \
+            or logits.numel() < batch * V:
+        raise ValueError("logits must hold `batch` contiguous rows")
+    if lp_cfg.dtype != torch.int32 or not lp_cfg.is_contiguous() \
+            or lp_cfg.numel() < batch:
+        raise ValueError("lp_cfg must be contiguous int32 with `batch` "
+                         "entries")
+    if stage.dtype != torch.float32 or not stage.is_contiguous() \
+            or stage.shape[-1] != LP_STAGE_WORDS \
+            or stage.numel() < batch * LP_STAGE_WORDS:
+        raise ValueError(f"stage must be contiguous fp32 "
+                         f"[>=batch, {LP_STAGE_WORDS}]")
+    if raw is not None and (
+            raw.dtype != torch.float32 or not raw.is_contiguous()
+            or raw.shape[-1] != V or raw.numel() < batch * V):
+        raise ValueError("raw must be contiguous fp32 [>=batch, V]")
+    return V, 1 if logits.dtype == torch.bfloat16 else 0
+
+
+def logprob_scan(logits: torch.Tensor, lp_cfg: torch.Tensor,
+                 part: torch.Tensor, stage: torch.Tensor,
+                 raw: torch.Tensor | None = None, batch: int = 1):
+    """Log-sum-exp and top-N of ``batch`` RAW logits rows (fp32 or bf16,
+    [batch, V] contiguous), ahead of ``logit_adjust`` / ``sample``.  Per
+    row b: ``lp_cfg[b]`` (int32; -1 = off, the row is not touched, else
+    its top-N, see ``logprob_set_cfg``), ``part[b]`` (int64
+    [``logprob_part_words(V)``] scratch, zero between launches) and
+    ``stage[b]`` (fp32 [LP_STAGE_WORDS]: row max, log-sum, top logits, top
+    ids).
+    ``raw`` (fp32 [batch, V], optional) receives a copy of every on row —
+    needed when the logits are adjusted in place before ``logprob_commit``
+    reads the sampled token's logit."""
+    V, lbf16 = _logprob_common(logits, lp_cfg, stage, raw, batch)
+    words = logprob_part_words(V)
+    if part.dtype != torch.int64 or not part.is_contiguous() \
+            or part.dim() != 2 or part.shape[-1] < words \
+            or part.shape[0] < batch:
+        raise ValueError(f"part must be contiguous int64 "
+                         f"[>=batch, >={words}]")
+    _check(lib().launch_logprob_scan(
+        _ptr(logits), V, lbf16, batch, _ptr(lp_cfg), _ptr(part),
+        part.shape[-1], _ptr(stage), _ptr(raw), _stream()), "logprob_scan")
+
+
+def logprob_commit(logits: torch.Tensor, lp_cfg: torch.Tensor,
+                   stage: torch.Tensor, next_token: torch.Tensor,
+                   nout: torch.Tensor, lp_val: torch.Tensor,
+                   lp_idx: torch.Tensor, raw: torch.Tensor | None = None,
+                   batch: int = 1):
+    """After ``sample``: for every on row b write record
+    ``(nout[b] - 1) % LP_RING`` — ``lp_val[b, slot]`` (fp32
+    [1 + LOGPROBS_MAX_TOP]: logprob of ``next_token[b]``, then the top-N)
+    and ``lp_idx[b, slot]`` (int32 [LOGPROBS_MAX_TOP] top ids).  The
+    sampled token's raw logit comes from ``raw`` when given (the step
+    adjusted the logits), else from ``logits``.  Slots j >= N keep what
+    they held; a row shorter than N fills id -1 / logprob -inf."""
+    V, lbf16 = _logprob_common(logits, lp_cfg, stage, raw, batch)
+    for name, t in (("next_token", next_token), ("nout", nout)):
+        if t.dtype != torch.int32 or not t.is_contiguous() \
+                or t.numel() < batch:
+            raise ValueError(f"{name} must be contiguous int32 with "
+                             f"`batch` entries")
+    W = LOGPROBS_MAX_TOP
+    if lp_val.dtype != torch.float32 or not lp_val.is_contiguous() \
+            or lp_val.numel() < batch * LP_RING * (1 + W) \
+            or tuple(lp_val.shape[-2:]) != (LP_RING, 1 + W):
+        raise ValueError(f"lp_val must be contiguous fp32 "
+                         f"[>=batch, {LP_RING}, {1 + W}]")
+    if lp_idx.dtype != torch.int32 or not lp_idx.is_contiguous() \
+            or lp_idx.numel() < batch * LP_RING * W \
+            or tuple(lp_idx.shape[-2:]) != (LP_RING, W):
+        raise ValueError(f"lp_idx must be contiguous int32 "
+                         f"[>=batch, {LP_RING}, {W}]")
+    _check(lib().launch_logprob_commit(
+        _ptr(logits), V, lbf16, batch, _ptr(lp_cfg), _ptr(stage), _ptr(raw),
+        _ptr(next_token), _ptr(nout), _ptr(lp_val), _ptr(lp_idx),
+        _stream()), "logprob_commit")
 
 
 def gemm(X: torch.Tensor, W: torch.Tensor, Y: torch.Tensor,

@@ -102,6 +102,24 @@ def _logprob_entry(logits: np.ndarray, chosen: int, top_n: int,
     }
 
 
+def logprob_entries(ids, records, top_n: int, tokenizer) -> List[dict]:
+    """Device logprob records ``(chosen_lp [n], top_ids [n, N], top_lp
+    [n, N])`` (``GPUModel.logprob_records`` / ``last_logprobs``; already
+    sorted descending) -> the entry dicts ``_logprob_entry`` builds, one
+    per id.  Slots the device left empty (vocabulary shorter than N: id
+    -1) are dropped."""
+    chosen_lp, top_ids, top_lp = records
+    out = []
+    for j, tok in enumerate(ids):
+        top = [{"id": int(i), "token": tokenizer.decode([int(i)]),
+                "logprob": float(v)}
+               for i, v in zip(top_ids[j][:top_n], top_lp[j][:top_n])
+               if int(i) >= 0]
+        out.append({"id": int(tok), "token": tokenizer.decode([int(tok)]),
+                    "logprob": float(chosen_lp[j]), "top": top})
+    return out
+
+
 def _truncate_at_stop(ids: List[int], tokenizer, stops: List[str]):
     """Earliest stop occurrence in decode(ids) -> (ids', text',
     hit).  The stop string itself is excluded (OpenAI semantics); ids'
@@ -134,14 +152,18 @@ def generate(prompt: str, tokenizer, model, max_tokens: int = 200,
     a stop string spanning token boundaries is never emitted.
 
     ``logprobs``: when an int N >= 0, GenerateResult.logprobs carries
-    per-token raw-model logprobs with the top-N alternatives (takes the
-    logits-visible step loop — the device-side sampler never surfaces
-    the full distribution).
+    per-token raw-model logprobs with the top-N alternatives.  An
+    engine that advertises ``device_logprobs`` >= N computes them inside
+    the decode graph (the fast path below, ``generate_tokens(...,
+    logprobs=N)``); a larger N, or any other engine, takes the
+    logits-visible step loop.
 
     Seeds: the GPU fast path's device sampler derives its stream from
     the ENGINE seed + a device counter (baked into the captured graph),
     so ``params.seed`` is honored on the logits-visible paths (CPU
-    oracle; logprobs requests; strategies or logit processors the
+    oracle; logprobs requests beyond the engine's ``device_logprobs`` —
+    within it they are device-sampled like every other fast-path request,
+    so ``params.seed`` is NOT honored; strategies or logit processors the
     engine does not list in ``device_strategies`` /
     ``device_processors``) but not by the in-graph device
     sampler — on an engine that advertises them that now includes
@@ -179,8 +201,13 @@ def generate(prompt: str, tokenizer, model, max_tokens: int = 200,
     # semantics, device RNG.  Engines that do not advertise
     # device_strategies get greedy / min-p only, with the original kwargs.
     # Penalties / logit_bias ride along when the engine advertises every
-    # active one in device_processors (the in-graph logit-adjust stage).
-    if (use_cache and logprobs is None
+    # active one in device_processors (the in-graph logit-adjust stage);
+    # logprobs when N is within the engine's device_logprobs (the in-graph
+    # logprob stage).
+    dev_lp = int(getattr(model, "device_logprobs", -1) or 0)
+    lp_on_device = (logprobs is not None and dev_lp > 0
+                    and 0 <= logprobs <= dev_lp)
+    if (use_cache and (logprobs is None or lp_on_device)
             and active_processors(params) <= frozenset(
                 getattr(model, "device_processors", ()))
             and hasattr(model, "generate_tokens")
@@ -202,17 +229,24 @@ def generate(prompt: str, tokenizer, model, max_tokens: int = 200,
             prompt_ids, max_tokens,
             eos_id=eos_set if stop_on_eos else None, on_ids=_emit,
             stop_fn=_stop_fn if stops else None,
-            **device_sampler_kwargs(params))
+            **device_sampler_kwargs(params),
+            **({"logprobs": int(logprobs)} if lp_on_device else {}))
         dt = time.perf_counter() - t0
         tp = getattr(model, "last_prefill_time_s", 0.0)
         hit_eos = bool(ids) and stop_on_eos and int(ids[-1]) in eos_set
         ids, text, reason = _finish(ids, hit_eos)
         if not stops and len(ids) >= max_tokens and not hit_eos:
             reason = "length"
+        lp_entries = None
+        if lp_on_device:
+            # one record per generated id; the stop-string cut above
+            # shortens the ids, the records follow
+            lp_entries = logprob_entries(ids, model.last_logprobs,
+                                         int(logprobs), tokenizer)
         return GenerateResult(text=text, token_ids=ids,
                               prefill_time_s=tp,
                               decode_time_s=max(dt - tp, 1e-9),
-                              finish_reason=reason)
+                              finish_reason=reason, logprobs=lp_entries)
 
     out_ids: List[int] = []
     t0 = time.perf_counter()

@@ -151,8 +151,11 @@ class BatchScheduler:
     def __init__(self, generate_one, run_group, max_batch: int,
                  window_s: float = 0.004,
                  device_strategies=("greedy", "min_p"),
-                 device_processors=()):
+                 device_processors=(), device_logprobs: int = 0):
         self.generate_one = generate_one
+        # largest top-N run_group's engine reports on device, per row —
+        # logprobs requests within it may join a group (0: none may)
+        self.device_logprobs = int(device_logprobs or 0)
         # logit processors (penalties / logit_bias) run_group's engine
         # applies on device, per row — such requests may join a group
         self.device_processors = frozenset(device_processors)
@@ -190,7 +193,9 @@ class BatchScheduler:
                 round(getattr(req, "top_p", 0.9), 6),
                 # processor VALUES are per-row device data: all requests
                 # with any processor share one group and one graph
-                bool(_req_processors(req)))
+                bool(_req_processors(req)),
+                # likewise N: one group and one graph serve mixed N
+                getattr(req, "logprobs", None) is not None)
 
     def _batchable(self, req) -> bool:
         # streaming and stop-string requests take the generate_one
@@ -200,10 +205,14 @@ class BatchScheduler:
                 and req.strategy in self.device_strategies
                 and not getattr(req, "stream", False)
                 and not getattr(req, "stop", None)
-                and getattr(req, "logprobs", None) is None
+                and self._logprobs_ok(getattr(req, "logprobs", None))
                 and _req_processors(req) <= self.device_processors
                 and not getattr(req, "echo", False)
                 and getattr(req, "n", 1) == 1)
+
+    def _logprobs_ok(self, n) -> bool:
+        return n is None or (self.device_logprobs > 0
+                             and 0 <= n <= self.device_logprobs)
 
     def _poll_compatible(self, key, deferred):
         """Non-blocking: next queued pending with this sampling key;
@@ -303,7 +312,10 @@ def build_app(model_name: str = "llama-3.2-1b", backend: str = "auto",
     scheduler logic is CPU-testable against a deterministic fake."""
     from fastapi import Body, FastAPI
 
+    import numpy as np
+
     import llm_np_cp_amd as L
+    from .generate import logprob_entries
     from .sampling import device_sampler_kwargs
 
     tok, model, cfg = L.load_model(model_name, backend=backend,
@@ -363,6 +375,14 @@ def build_app(model_name: str = "llama-3.2-1b", backend: str = "auto",
             },
         }
 
+    def _logprobs_block(entries) -> dict:
+        return {
+            "tokens": [e["token"] for e in entries],
+            "token_logprobs": [e["logprob"] for e in entries],
+            "top_logprobs": [{t["token"]: t["logprob"] for t in e["top"]}
+                             for e in entries],
+        }
+
     def generate_one(req, on_token=None) -> dict:
         n = getattr(req, "n", 1) or 1
         t0 = time.time()
@@ -391,24 +411,19 @@ def build_app(model_name: str = "llama-3.2-1b", backend: str = "auto",
                 if metrics_reg is not None:  # extra choices count too
                     m_tokens.inc(len(out.token_ids))
             if out.logprobs is not None:
-                pay["choices"][idx]["logprobs"] = {
-                    "tokens": [e["token"] for e in out.logprobs],
-                    "token_logprobs": [e["logprob"]
-                                       for e in out.logprobs],
-                    "top_logprobs": [{t["token"]: t["logprob"]
-                                      for t in e["top"]}
-                                     for e in out.logprobs],
-                }
+                pay["choices"][idx]["logprobs"] = _logprobs_block(
+                    out.logprobs)
         pay["timings"]["total_s"] = time.time() - t0
         return pay
 
     class _Row:
-        __slots__ = ("pending", "ids", "first_consumed")
+        __slots__ = ("pending", "ids", "first_consumed", "lp")
 
         def __init__(self, pending):
             self.pending = pending
             self.ids = []
             self.first_consumed = False
+            self.lp = []  # per chunk (chosen_lp, top_ids, top_lp)
 
     def run_group(pendings, poll, stats) -> None:
         """Continuous ragged batching: chunks of 16 steps; retired rows
@@ -434,6 +449,11 @@ def build_app(model_name: str = "llama-3.2-1b", backend: str = "auto",
         # bias (device data), the decode graph just carries the stage
         with_proc = bool(_req_processors(r0))
         dkw = dict(skw, processors=True) if with_proc else skw
+        # a logprobs group (_key): each row brings its OWN top-N (device
+        # data); its records are gathered chunk by chunk
+        with_lp = getattr(r0, "logprobs", None) is not None
+        if with_lp:
+            dkw = dict(dkw, logprobs=True)
         rows: list = []  # slot -> _Row
 
         def admit(p):
@@ -450,6 +470,8 @@ def build_app(model_name: str = "llama-3.2-1b", backend: str = "auto",
                     p.error = e
                     p.done.set()
                     return
+            if with_lp:
+                pkw = dict(pkw, logprobs=int(p.req.logprobs))
             model.prefill_row(slot, tok.encode(p.req.prompt), **pkw)
             p.prefill_s = time.time() - t_p
             rows.append(_Row(p))
@@ -462,6 +484,14 @@ def build_app(model_name: str = "llama-3.2-1b", backend: str = "auto",
             p.result = _payload(p.req, ids, tok.decode(ids), dt,
                                 getattr(p, "prefill_s", 0.0),
                                 len(ids) / max(dt, 1e-9))
+            if with_lp:
+                N = int(p.req.logprobs)
+                rec = tuple(np.concatenate([c[j] for c in row.lp])
+                            for j in range(3)) if row.lp else (
+                    np.zeros(0, np.float32), np.zeros((0, N), np.int32),
+                    np.zeros((0, N), np.float32))
+                p.result["choices"][0]["logprobs"] = _logprobs_block(
+                    logprob_entries(ids, rec, N, tok))
             p.done.set()
 
         for p in pendings:
@@ -490,6 +520,7 @@ def build_app(model_name: str = "llama-3.2-1b", backend: str = "auto",
             # the first sampled token (from prefill_row) precedes chunk 1
             for b in range(B):
                 row = rows[b]
+                have = len(row.ids)
                 if not row.first_consumed:
                     # ring holds first+chunk ids; decode_rows returned
                     # the last `chunk` — prepend the first token once
@@ -500,6 +531,11 @@ def build_app(model_name: str = "llama-3.2-1b", backend: str = "auto",
                         row.ids.append(first_id)
                     row.first_consumed = True
                 row.ids.extend(int(t) for t in out[b])
+                if with_lp:
+                    # one record per id this chunk added (first token
+                    # included)
+                    row.lp.append(model.logprob_records(
+                        len(row.ids) - have, row=b))
             # retire rows (EOS / max_tokens), compacting from the end
             b = 0
             while b < len(rows):
@@ -528,8 +564,11 @@ def build_app(model_name: str = "llama-3.2-1b", backend: str = "auto",
                                model, "device_strategies",
                                ("greedy", "min_p")),
                            device_processors=getattr(
-                               model, "device_processors", ()))
+                               model, "device_processors", ()),
+                           device_logprobs=getattr(
+                               model, "device_logprobs", 0))
     app = FastAPI(title="llm_np_cp_amd", version=L.__version__)
+    app.state.scheduler = sched  # in-process callers (and tests) queue here
 
     @app.get("/v1/models")
     def models():
