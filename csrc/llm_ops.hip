@@ -2580,16 +2580,10 @@ DEVINL int unpack_idx(uint64_t p) { return 0x7fffffff - (int)(uint32_t)p; }
 // pass 1 (min-p only): global max logit -> gmax[b] (packed).
 // Batched: grid.y = sequence row b (lbf16: logits stored bf16 — the
 // batched lm_head GEMM path emits bf16 rows).
-extern "C" __global__ void __launch_bounds__(256)
-k_logit_max(const void* __restrict__ logits, int V, int lbf16,
-            unsigned long long* __restrict__ gmax,
-            uint64_t* __restrict__ ctr) {
+DEVINL void logit_max_body(const void* __restrict__ logits, int V, int lbf16,
+                           unsigned long long* __restrict__ gmax) {
   const int b = blockIdx.y;
   gmax += b;
-  // advance the shared RNG counter HERE: stream order guarantees every
-  // k_sample_pick block then reads the same post-bump value (bumping
-  // from pick's commit raced with straggler blocks still reading it)
-  if (ctr && blockIdx.x == 0 && b == 0 && threadIdx.x == 0) *ctr += 1;
   const float* lf = (const float*)logits + (size_t)b * V;
   const u16* lh = (const u16*)logits + (size_t)b * V;
   float mv = -INFINITY;
@@ -2614,6 +2608,40 @@ k_logit_max(const void* __restrict__ logits, int V, int lbf16,
   }
 }
 
+extern "C" __global__ void __launch_bounds__(256)
+k_logit_max(const void* __restrict__ logits, int V, int lbf16,
+            unsigned long long* __restrict__ gmax,
+            uint64_t* __restrict__ ctr) {
+  // advance the shared RNG counter HERE: stream order guarantees every
+  // k_sample_pick block then reads the same post-bump value (bumping
+  // from pick's commit raced with straggler blocks still reading it)
+  if (ctr && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)
+    *ctr += 1;
+  logit_max_body(logits, V, lbf16, gmax);
+}
+
+// Per-row sampler table `samp` [rows, SAMP_WORDS] u32: the sampler's
+// parameters as device DATA, so rows with different strategies /
+// temperatures / seeds share one launch sequence and one captured graph.
+#define SAMP_MODE 0  // 0 greedy, 1 min-p cut, 2 top-k, 3 top-p
+#define SAMP_INVT 1  // fp32 1 / temperature
+#define SAMP_MINP 2  // fp32 (mode 1; 0 = plain temperature sampling)
+#define SAMP_TOPK 3  // int, 1..V (mode 2)
+#define SAMP_TOPP 4  // fp32 (mode 3)
+#define SAMP_SEED 5  // 5, 6: the row's 64-bit seed (lo, hi)
+#define SAMP_CTR 7   // draws so far: zeroed by the host, advanced here
+#define SAMP_WORDS 8
+
+// k_logit_max per row of `samp`: each row's own draw counter advances
+// (same stream-order argument as above); the shared counter is not used.
+extern "C" __global__ void __launch_bounds__(256)
+k_logit_max_rows(const void* __restrict__ logits, int V, int lbf16,
+                 unsigned long long* __restrict__ gmax, uint32_t* samp) {
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+    samp[(size_t)blockIdx.y * SAMP_WORDS + SAMP_CTR] += 1u;
+  logit_max_body(logits, V, lbf16, gmax);
+}
+
 // pass 2: winner = argmax over kept tokens of (logit/T [+ Gumbel]) -> *pick,
 // and the LAST-arriving block (G16 ticket) commits it: write *next_token,
 // append to out_ring, bump len/ctr, re-zero the scratch — the former
@@ -2630,6 +2658,59 @@ k_logit_max(const void* __restrict__ logits, int V, int lbf16,
 #define SEL_TICKET 3  // last-arriver ticket of the running pass
 #define SEL_HIST 4    // 256-bin u64 histogram (count or fixed-point mass)
 #define SEL_WORDS 260
+
+// block winner (bv, bi) -> *pick; the last-arriving block commits.  All
+// pointers are the ROW's own except next_token / len_ptr (indexed by b);
+// sel != nullptr: the row ran the selection stage, re-arm its result words.
+DEVINL void sample_pick_commit(
+    float bv, int bi, int V, unsigned long long* __restrict__ gmax,
+    unsigned long long* __restrict__ pick, int* __restrict__ cnt,
+    int* __restrict__ next_token, int* __restrict__ out_ring,
+    int* __restrict__ nout, int* __restrict__ len_ptr, int bump_len,
+    unsigned long long* __restrict__ sel) {
+  const int b = blockIdx.y;
+  uint64_t pk = pack_ki(fkey(bv), bi);
+#pragma unroll
+  for (int w = 1; w < 64; w <<= 1) {
+    uint64_t o = __shfl_xor((unsigned long long)pk, w);
+    if (o > pk) pk = o;
+  }
+  __shared__ unsigned long long ws[4];
+  __shared__ int lastflag;
+  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = pk;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint64_t b = ws[0];
+    for (int w = 1; w < 4; w++) if (ws[w] > b) b = ws[w];
+    atomicMax(pick, (unsigned long long)b);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    int t = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_ACQ_REL,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+    lastflag = (t == (int)gridDim.x - 1);
+  }
+  __syncthreads();
+  if (!lastflag || threadIdx.x != 0) return;
+  // last arriver: commit the winner, reset scratch, advance state
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  *cnt = 0;
+  int winner = unpack_idx(
+      __hip_atomic_load(pick, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+  if (winner < 0 || winner >= V) winner = 0;  // NaN-logit insurance
+  next_token[b] = winner;
+  int n = *nout;
+  out_ring[n] = winner;
+  *nout = n + 1;
+  // per-row position advances (ragged batch); the shared RNG counter
+  // was already advanced by k_logit_max ahead of this kernel
+  if (bump_len) len_ptr[b] += 1;
+  *pick = 0ull;
+  *gmax = 0ull;
+  if (sel) {
+    sel[SEL_TAU] = 0ull;
+    sel[SEL_PREFIX] = 0ull;
+    sel[SEL_TARGET] = 0ull;
+  }
+}
 
 template <bool SEL>
 DEVINL void sample_pick_body(
@@ -2671,47 +2752,8 @@ DEVINL void sample_pick_body(
     }
     if (sc > bv || (sc == bv && i < bi)) { bv = sc; bi = i; }
   }
-  uint64_t pk = pack_ki(fkey(bv), bi);
-#pragma unroll
-  for (int w = 1; w < 64; w <<= 1) {
-    uint64_t o = __shfl_xor((unsigned long long)pk, w);
-    if (o > pk) pk = o;
-  }
-  __shared__ unsigned long long ws[4];
-  __shared__ int lastflag;
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = pk;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint64_t b = ws[0];
-    for (int w = 1; w < 4; w++) if (ws[w] > b) b = ws[w];
-    atomicMax(pick, (unsigned long long)b);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    int t = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_ACQ_REL,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-    lastflag = (t == (int)gridDim.x - 1);
-  }
-  __syncthreads();
-  if (!lastflag || threadIdx.x != 0) return;
-  // last arriver: commit the winner, reset scratch, advance state
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  *cnt = 0;
-  int winner = unpack_idx(
-      __hip_atomic_load(pick, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-  if (winner < 0 || winner >= V) winner = 0;  // NaN-logit insurance
-  next_token[b] = winner;
-  int n = *nout;
-  out_ring[n] = winner;
-  *nout = n + 1;
-  // per-row position advances (ragged batch); the shared RNG counter
-  // was already advanced by k_logit_max ahead of this kernel
-  if (bump_len) len_ptr[b] += 1;
-  *pick = 0ull;
-  *gmax = 0ull;
-  if (SEL) {
-    sel[SEL_TAU] = 0ull;
-    sel[SEL_PREFIX] = 0ull;
-    sel[SEL_TARGET] = 0ull;
-  }
+  sample_pick_commit(bv, bi, V, gmax, pick, cnt, next_token, out_ring, nout,
+                     len_ptr, bump_len, SEL ? sel : nullptr);
 }
 
 extern "C" __global__ void __launch_bounds__(256)
@@ -2745,6 +2787,61 @@ k_sample_pick_sel(const void* __restrict__ logits, int V, int lbf16,
                          out_ring, nout, len_ptr, bump_len, sel);
 }
 
+// Per-row variant: mode, temperature, cut and seed come from samp[b], so
+// one launch serves rows of every strategy.  Keep-set per mode: 0 all
+// (plain argmax), 1 the min-p expression of k_sample_pick, 2 / 3
+// {fkey(l) >= tau} with tau from k_sample_select_rows.  The noise of
+// element i is a function of (i, row seed, row counter) alone — neither
+// the slot b nor a shared counter enters — so a request's stream does not
+// depend on where it sits or on what its neighbours do.
+extern "C" __global__ void __launch_bounds__(256)
+k_sample_pick_rows(const void* __restrict__ logits, int V, int lbf16,
+                   long ring_stride, const uint32_t* __restrict__ samp,
+                   unsigned long long* __restrict__ gmax,
+                   unsigned long long* __restrict__ pick,
+                   int* __restrict__ cnt, int* __restrict__ next_token,
+                   int* __restrict__ out_ring, int* __restrict__ nout,
+                   int* __restrict__ len_ptr, int bump_len,
+                   unsigned long long* __restrict__ sel) {
+  const int b = blockIdx.y;
+  gmax += b; pick += b; cnt += b; nout += b;
+  out_ring += (size_t)b * ring_stride;
+  sel += (size_t)b * SEL_WORDS;
+  samp += (size_t)b * SAMP_WORDS;
+  const float* lf = (const float*)logits + (size_t)b * V;
+  const u16* lh = (const u16*)logits + (size_t)b * V;
+  const uint32_t mode = samp[SAMP_MODE];
+  const float inv_temp = __uint_as_float(samp[SAMP_INVT]);
+  const bool greedy = mode == 0u;
+  const bool selected = mode >= 2u;
+  float thresh = -INFINITY;
+  uint32_t tau = 0;
+  if (selected)
+    tau = (uint32_t)sel[SEL_TAU];
+  else if (!greedy)
+    thresh = fkey_inv((uint32_t)(*gmax >> 32)) +
+             __logf(__uint_as_float(samp[SAMP_MINP])) / inv_temp;
+  // two per-draw keys: k0 mixes counter and seed lo, k1 adds seed hi
+  const uint32_t k0 =
+      hash32(hash32(samp[SAMP_CTR] ^ 0x9e3779b9u) ^ samp[SAMP_SEED]);
+  const uint32_t k1 = hash32(k0 ^ samp[SAMP_SEED + 1] ^ 0x85ebca6bu);
+  float bv = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < V; i += gridDim.x * 256) {
+    float v = lbf16 ? b2f(lh[i]) : lf[i];
+    if (selected ? (fkey(v) < tau) : (v < thresh)) continue;
+    float sc = v;
+    if (!greedy) {
+      uint32_t r = hash32(hash32((uint32_t)i ^ k0) ^ k1);
+      float u = (r + 1.0f) * 2.3283064e-10f;  // (0,1]
+      sc = v * inv_temp - __logf(-__logf(u));
+    }
+    if (sc > bv || (sc == bv && i < bi)) { bv = sc; bi = i; }
+  }
+  sample_pick_commit(bv, bi, V, gmax, pick, cnt, next_token, out_ring, nout,
+                     len_ptr, bump_len, selected ? sel : nullptr);
+}
+
 // Selection stage for top-k / top-p: one pass of an MSB-first radix
 // select over fkey(logit), 8 bits per pass (launched 4x: shift 24,16,8,0;
 // bf16 rows 2x: their keys' low 16 bits are zero, so bin 0 is known).
@@ -2760,11 +2857,11 @@ k_sample_pick_sel(const void* __restrict__ logits, int V, int lbf16,
 // the `last` pass the prefix is the threshold key tau (ties at tau are
 // kept).  A row that cannot reach its target (all-NaN / zero mass) falls
 // to bin 0 every pass: tau = 0 keeps everything, nothing loops.
-extern "C" __global__ void __launch_bounds__(256)
-k_sample_select(const void* __restrict__ logits, int V, int lbf16,
-                int top_k, float top_p, float inv_temp, int shift,
-                int last, const unsigned long long* __restrict__ gmax,
-                unsigned long long* __restrict__ sel) {
+DEVINL void sample_select_body(
+    const void* __restrict__ logits, int V, int lbf16,
+    int top_k, float top_p, float inv_temp, int shift,
+    int last, const unsigned long long* __restrict__ gmax,
+    unsigned long long* __restrict__ sel) {
   const int b = blockIdx.y;
   const int t = threadIdx.x;
   sel += (size_t)b * SEL_WORDS;
@@ -2849,6 +2946,34 @@ k_sample_select(const void* __restrict__ logits, int V, int lbf16,
   }
 }
 
+extern "C" __global__ void __launch_bounds__(256)
+k_sample_select(const void* __restrict__ logits, int V, int lbf16,
+                int top_k, float top_p, float inv_temp, int shift,
+                int last, const unsigned long long* __restrict__ gmax,
+                unsigned long long* __restrict__ sel) {
+  sample_select_body(logits, V, lbf16, top_k, top_p, inv_temp, shift, last,
+                     gmax, sel);
+}
+
+// Per-row variant: weight and first-pass target follow samp[b]'s mode
+// (2: count / top_k, 3: fixed-point mass / top_p at the row's own
+// temperature), so top-k and top-p rows share the same passes.  A row in
+// mode 0 / 1 returns at once: neither its sel words nor its ticket are
+// touched (the whole block leaves, so no barrier is left waiting).
+extern "C" __global__ void __launch_bounds__(256)
+k_sample_select_rows(const void* __restrict__ logits, int V, int lbf16,
+                     const uint32_t* __restrict__ samp, int shift, int last,
+                     const unsigned long long* __restrict__ gmax,
+                     unsigned long long* __restrict__ sel) {
+  samp += (size_t)blockIdx.y * SAMP_WORDS;
+  const uint32_t mode = samp[SAMP_MODE];
+  if (mode < 2u) return;
+  sample_select_body(logits, V, lbf16,
+                     mode == 2u ? (int)samp[SAMP_TOPK] : 0,
+                     __uint_as_float(samp[SAMP_TOPP]),
+                     __uint_as_float(samp[SAMP_INVT]), shift, last, gmax, sel);
+}
+
 extern "C" hipError_t launch_sample(const void* logits, int V, int lbf16,
                                     int batch, long ring_stride, float min_p,
                                     int greedy, uint64_t seed, float inv_temp,
@@ -2917,6 +3042,62 @@ extern "C" hipError_t launch_sample_sel(
   hipLaunchKernelGGL(k_sample_pick_sel, dim3(blocks, batch), dim3(256), 0,
                      stream, logits, V, lbf16, ring_stride, seed, inv_temp,
                      (unsigned long long*)gmax, (uint64_t*)ctr,
+                     (unsigned long long*)pick, (int*)cnt, (int*)next_token,
+                     (int*)out_ring, (int*)nout, (int*)len_ptr, bump_len,
+                     (unsigned long long*)sel);
+  return hipGetLastError();
+}
+
+// Sampler driven by the per-row table `samp` ([batch, SAMP_WORDS] u32).
+// The host knows the union of the rows' modes and launches only what it
+// needs, with the grids of launch_sample / launch_sample_sel:
+//   no sampled row (all mode 0):   k_sample_pick greedy — exactly the
+//                                  launch_sample greedy launch
+//   no row in mode 2 / 3:          max + pick
+//   else:                          max + 4 (bf16: 2) select passes + pick
+// so a uniform group costs the launches it costs through the legacy
+// launchers.  A row whose mode the flags do not cover is a host error
+// (its keep-set would be the whole row).
+extern "C" hipError_t launch_sample_rows(
+    const void* logits, int V, int lbf16, int batch, long ring_stride,
+    void* samp, int any_sampled, int any_select, void* gmax, void* pick,
+    void* cnt, void* next_token, void* out_ring, void* nout, void* len_ptr,
+    int bump_len, void* sel, hipStream_t stream) {
+  int blocks = (V + 255) / 256;
+  if (blocks > 512) blocks = 512;
+  if (batch > 1) {
+    blocks = blocks / batch + 1;
+    if (blocks < 16) blocks = 16;
+  }
+  if (!any_sampled && !any_select) {
+    // greedy reads neither seed nor counter value; `samp` only stands in
+    // as a readable 8-byte word for the kernel's counter load
+    hipLaunchKernelGGL(k_sample_pick, dim3(blocks, batch), dim3(256), 0,
+                       stream, logits, V, lbf16, ring_stride, 0.0f, 1,
+                       (uint64_t)0, 1.0f, (unsigned long long*)gmax,
+                       (uint64_t*)samp, (unsigned long long*)pick, (int*)cnt,
+                       (int*)next_token, (int*)out_ring, (int*)nout,
+                       (int*)len_ptr, bump_len);
+    return hipGetLastError();
+  }
+  hipLaunchKernelGGL(k_logit_max_rows, dim3(blocks, batch), dim3(256), 0,
+                     stream, logits, V, lbf16, (unsigned long long*)gmax,
+                     (uint32_t*)samp);
+  if (any_select) {
+    int sblocks = (V + 2047) / 2048;
+    if (sblocks > 64) sblocks = 64;
+    const int last_shift = lbf16 ? 16 : 0;
+    for (int shift = 24; shift >= last_shift; shift -= 8)
+      hipLaunchKernelGGL(k_sample_select_rows, dim3(sblocks, batch),
+                         dim3(256), 0, stream, logits, V, lbf16,
+                         (const uint32_t*)samp, shift,
+                         shift == last_shift ? 1 : 0,
+                         (const unsigned long long*)gmax,
+                         (unsigned long long*)sel);
+  }
+  hipLaunchKernelGGL(k_sample_pick_rows, dim3(blocks, batch), dim3(256), 0,
+                     stream, logits, V, lbf16, ring_stride,
+                     (const uint32_t*)samp, (unsigned long long*)gmax,
                      (unsigned long long*)pick, (int*)cnt, (int*)next_token,
                      (int*)out_ring, (int*)nout, (int*)len_ptr, bump_len,
                      (unsigned long long*)sel);

@@ -51,6 +51,11 @@ class GPUModel:
     # largest top-N the in-graph logprob stage reports per token (set per
     # instance: LOGPROBS_MAX_TOP at world == 1, 0 under tensor parallel)
     device_logprobs = 0
+    # the sampler reads strategy / temperature / filter / seed per row
+    # from device memory (``row_sampler=``): requests with different
+    # sampler settings share one lockstep group and one captured graph,
+    # and ``seed`` is honored (set per instance: True at world == 1)
+    device_row_sampler = False
 
     def __init__(self, config: ModelConfig, weights: Dict[str, np.ndarray],
                  dtype: str = "bf16", max_seq: Optional[int] = 4096,
@@ -120,6 +125,16 @@ class GPUModel:
         self._lp_rows = {}
         self._lp_batch = False  # records follow bt_nout (else nout)
         self.last_logprobs = None
+        if self.world == 1:
+            self.device_row_sampler = True
+        # host mirror of the per-row sampler table: slot -> mode of every
+        # lockstep slot set up with ``row_sampler`` (the launcher is told
+        # which stages the rows present need); _req_serial numbers the
+        # requests that came without a seed of their own
+        self._samp_modes = {}
+        self._req_serial = 0
+        # mode set of the single-sequence table row (all zero = greedy)
+        self._s_rows = frozenset({0})
         if device is None:
             device = f"cuda:{self.rank % max(torch.cuda.device_count(), 1)}"
         self.device = torch.device(device)
@@ -459,6 +474,9 @@ class GPUModel:
         self.nout = torch.zeros(1, **i32)
         self.len_buf = torch.zeros(1, **i32)
         self.rng_ctr = torch.zeros(1, dtype=torch.int64, device=dev)
+        # per-row sampler table (mode, 1/T, min_p, top_k, top_p, seed,
+        # draw counter) of the single-sequence path
+        self.s_samp = torch.zeros(1, ho.SAMP_WORDS, **i32)
 
         if self.max_batch > 1:
             B, nhh = self.max_batch, self.nh_l * hd
@@ -476,6 +494,7 @@ class GPUModel:
             self.bt_pick = torch.zeros(B, **i64)
             self.bt_cnt = torch.zeros(B, **i32)
             self.bt_sel = torch.zeros(B, ho.SAMPLE_SEL_WORDS, **i64)
+            self.bt_samp = torch.zeros(B, ho.SAMP_WORDS, **i32)
             self.bt_scratch = torch.zeros(
                 B * self.nh_l * self.attn_split * (hd + 2),
                 dtype=torch.float32, device=dev)
@@ -1031,12 +1050,84 @@ class GPUModel:
         idx = self.lp_idx[row].cpu().numpy()[slots]
         return (val[:, 0].copy(), idx[:, :N].copy(), val[:, 1:1 + N].copy())
 
+    # ------------------------------------------------------------------
+    # per-row sampler: strategy / temperature / filter / seed as device data
+    # ------------------------------------------------------------------
+    def _samp_pack(self, row_sampler):
+        """``row_sampler`` dict (``sampling.device_row_sampler_kwargs``:
+        strategy fields + optional ``seed``) -> (table row as int32[8] host
+        tensor, mode).  Raises ValueError on bad values, ahead of any
+        launch.  A request without a seed gets one from the engine seed
+        and a per-engine request serial, so two identical unseeded
+        requests draw different streams (and a re-run of the same engine
+        repeats them)."""
+        assert self.world == 1, "the per-row sampler is single-GPU"
+        seed = row_sampler.get("seed")
+        words = ho.samp_row(row_sampler, 0 if seed is None else seed,
+                            self.config.vocab_size)
+        if seed is None:
+            # splitmix64 of (engine seed, serial)
+            z = (int(self.seed) * 0x9E3779B97F4A7C15
+                 + (self._req_serial + 1) * 0xD1B54A32D192ED03) & (2**64 - 1)
+            self._req_serial += 1
+            z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & (2**64 - 1)
+            z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & (2**64 - 1)
+            z ^= z >> 31
+            words[5], words[6] = z & 0xFFFFFFFF, z >> 32
+        return torch.from_numpy(words.view(np.int32)), int(words[0])
+
+    def _row_modes(self, B: int) -> frozenset:
+        """Modes present in lockstep rows [0, B) (host mirror)."""
+        missing = [b for b in range(B) if b not in self._samp_modes]
+        if missing:
+            raise ValueError(f"rows {missing} were not set up with "
+                             f"prefill_row(row_sampler=...)")
+        return frozenset(self._samp_modes[b] for b in range(B))
+
+    @staticmethod
+    def _rows_key(rows) -> tuple:
+        """What of a mode set shapes the launch sequence: (any sampled
+        row, any top-k / top-p row).  No parameter VALUE is part of it."""
+        return (bool(rows - {ho.SAMP_GREEDY}),
+                bool(rows & {ho.SAMP_TOP_K, ho.SAMP_TOP_P}))
+
+    def _sample_step(self, greedy, min_p, temperature, top_k, top_p, rows):
+        """Sampler of the single-sequence decode step (``rows``: the mode
+        set of a ``row_sampler`` run, else the legacy arguments)."""
+        if rows is None:
+            ho.sample(self.b_logits, min_p, greedy, self.seed, self.rng_ctr,
+                      self.s_gmax, self.s_pick, self.next_token,
+                      self.out_ring, self.nout, self.len_buf, bump_len=True,
+                      temperature=temperature, cnt=self.s_cnt,
+                      top_k=top_k, top_p=top_p, sel=self.s_sel)
+        else:
+            ho.sample_rows(self.b_logits, self.s_samp, self.s_gmax,
+                           self.s_pick, self.s_cnt, self.next_token,
+                           self.out_ring, self.nout, self.len_buf,
+                           self.s_sel, 1, True, rows)
+
+    def _sample_batch_step(self, B, greedy, min_p, temperature, top_k,
+                           top_p, rows):
+        """Sampler of a lockstep decode step over bt_logits[:B]."""
+        if rows is None:
+            ho.sample(self.bt_logits[:B], min_p, greedy, self.seed,
+                      self.rng_ctr, self.bt_gmax, self.bt_pick, self.bt_next,
+                      self.bt_ring, self.bt_nout, self.bt_lens,
+                      bump_len=True, temperature=temperature,
+                      cnt=self.bt_cnt, batch=B,
+                      top_k=top_k, top_p=top_p, sel=self.bt_sel)
+        else:
+            ho.sample_rows(self.bt_logits[:B], self.bt_samp, self.bt_gmax,
+                           self.bt_pick, self.bt_cnt, self.bt_next,
+                           self.bt_ring, self.bt_nout, self.bt_lens,
+                           self.bt_sel, B, True, rows)
+
     def generate_tokens(self, prompt_ids, max_tokens: int,
                         greedy: bool = True, min_p: float = 0.1,
                         eos_id=None, chunk: int = 16, on_ids=None,
                         temperature: float = 1.0, stop_fn=None,
                         top_k: int = 0, top_p: float = 1.0,
-                        processors=None, logprobs=None):
+                        processors=None, logprobs=None, row_sampler=None):
         """Fast generate: device-side hipGraph decode in chunks, host
         sees ids every `chunk` tokens (streaming + EOS stop).  Used by
         runtime.generate() for every strategy in ``device_strategies``
@@ -1050,6 +1141,11 @@ class GPUModel:
         distribution (before processors / temperature), one row per
         returned id (a caller that truncates the ids on a stop string
         truncates them alike); None when logprobs were not asked for.
+        ``row_sampler`` (dict of ``sampling.device_row_sampler_kwargs``:
+        ``strategy`` and its fields, optional ``seed``) replaces greedy /
+        min_p / temperature / top_k / top_p: the sampler reads them from
+        the device table, and the stream is a function of the seed alone
+        (same seed, same tokens).
         ``eos_id`` may be an int or a collection of ints (HF configs
         often store a list, e.g. Llama-3.2-Instruct).  ``stop_fn``
         (optional) sees the accumulated ids after each chunk and returns
@@ -1065,9 +1161,16 @@ class GPUModel:
         eos_set = (set() if eos_id is None else
                    {int(eos_id)} if np.isscalar(eos_id) else
                    {int(e) for e in eos_id})
+        rskw = {}
+        if row_sampler is not None:
+            words, mode = self._samp_pack(row_sampler)
+            self._s_rows = frozenset({mode})
+            rskw = {"row_sampler": True}
         t0 = _time.perf_counter()
         with trace_range("prefill"):
             self.prefill(prompt_ids)
+            if row_sampler is not None:
+                self.s_samp[0].copy_(words)  # draw counter back to 0
             if processors is not None:
                 self.setup_processors(0, prompt_ids, processors)
             if logprobs is not None:
@@ -1087,7 +1190,8 @@ class GPUModel:
                                   use_graph=True, first_from_logits=first,
                                   temperature=temperature, top_k=top_k,
                                   top_p=top_p,
-                                  processors=processors is not None, **lpkw)
+                                  processors=processors is not None, **lpkw,
+                                  **rskw)
                 first = False
                 produced += n
                 stop = False
@@ -1172,7 +1276,7 @@ class GPUModel:
     def _decode_step(self, greedy: bool, min_p: float,
                      temperature: float = 1.0, top_k: int = 0,
                      top_p: float = 1.0, proc: bool = False,
-                     logprobs: bool = False):
+                     logprobs: bool = False, rows=None):
         """Fused decode path: 4 kernels/layer (llama) or 5 (gemma) —
         RMSNorm lives inside the GEMV staging pass, RoPE + KV write
         inside the attention kernel.  bf16 weights: the gate+up GEMV
@@ -1338,11 +1442,7 @@ class GPUModel:
             # the history, then penalties + bias in place
             ho.logit_adjust(self.b_logits, self.p_stat, self.p_proc,
                             self.p_bias, self.next_token, True)
-        ho.sample(self.b_logits, min_p, greedy, self.seed, self.rng_ctr,
-                  self.s_gmax, self.s_pick, self.next_token, self.out_ring,
-                  self.nout, self.len_buf, bump_len=True,
-                  temperature=temperature, cnt=self.s_cnt,
-                  top_k=top_k, top_p=top_p, sel=self.s_sel)
+        self._sample_step(greedy, min_p, temperature, top_k, top_p, rows)
         if logprobs:
             self._lp_commit(self.b_logits, slice(0, 1), proc,
                             self.next_token, self.nout)
@@ -1353,7 +1453,7 @@ class GPUModel:
     def _decode_batch_step(self, B: int, greedy: bool, min_p: float,
                            temperature: float = 1.0, top_k: int = 0,
                            top_p: float = 1.0, proc: bool = False,
-                           logprobs: bool = False):
+                           logprobs: bool = False, rows=None):
         """One decode step for B lockstep sequences.  fp8 weights with
         B<=8 take the fused MULTI-X GEMV path (one weight stream feeds
         B accumulators — near single-sequence step time); otherwise the
@@ -1370,11 +1470,13 @@ class GPUModel:
         if (self.fp8 and B <= mx_max and not cfg.attention_bias
                 and not self.moe):
             return self._decode_batch_step_mx(B, greedy, min_p, temperature,
-                                              top_k, top_p, proc, logprobs)
+                                              top_k, top_p, proc, logprobs,
+                                              rows)
         if self.fp8 and B <= 16 and not self.moe:
             return self._decode_batch_step_skinny(B, greedy, min_p,
                                                   temperature, top_k,
-                                                  top_p, proc, logprobs)
+                                                  top_p, proc, logprobs,
+                                                  rows)
         ho.embed(self.embed, self.bt_next, self.b_h, B, cfg.embed_scale)
         self._layers_forward(B, batch_attn=True)
         ho.rmsnorm(self.b_h[:B], self.g_final, self.b_xn[:B],
@@ -1393,11 +1495,8 @@ class GPUModel:
             self._lp_scan(self.bt_logits[:B], slice(0, B), proc)
         if proc:
             self._adjust_rows(B)
-        ho.sample(self.bt_logits[:B], min_p, greedy, self.seed,
-                  self.rng_ctr, self.bt_gmax, self.bt_pick, self.bt_next,
-                  self.bt_ring, self.bt_nout, self.bt_lens, bump_len=True,
-                  temperature=temperature, cnt=self.bt_cnt, batch=B,
-                  top_k=top_k, top_p=top_p, sel=self.bt_sel)
+        self._sample_batch_step(B, greedy, min_p, temperature, top_k, top_p,
+                                rows)
         if logprobs:
             self._lp_commit(self.bt_logits[:B], slice(0, B), proc,
                             self.bt_next, self.bt_nout)
@@ -1405,7 +1504,7 @@ class GPUModel:
     def _decode_batch_step_mx(self, B: int, greedy: bool, min_p: float,
                               temperature: float = 1.0, top_k: int = 0,
                               top_p: float = 1.0, proc: bool = False,
-                              logprobs: bool = False):
+                              logprobs: bool = False, rows=None):
         """Fused batched decode (fp8, B<=8): mirrors _decode_step's
         4-5 kernels/layer with multi-x GEMVs over B rows."""
         cfg = self.config
@@ -1482,11 +1581,8 @@ class GPUModel:
             self._lp_scan(self.bt_logits[:B], slice(0, B), proc)
         if proc:
             self._adjust_rows(B)
-        ho.sample(self.bt_logits[:B], min_p, greedy, self.seed,
-                  self.rng_ctr, self.bt_gmax, self.bt_pick, self.bt_next,
-                  self.bt_ring, self.bt_nout, self.bt_lens, bump_len=True,
-                  temperature=temperature, cnt=self.bt_cnt, batch=B,
-                  top_k=top_k, top_p=top_p, sel=self.bt_sel)
+        self._sample_batch_step(B, greedy, min_p, temperature, top_k, top_p,
+                                rows)
         if logprobs:
             self._lp_commit(self.bt_logits[:B], slice(0, B), proc,
                             self.bt_next, self.bt_nout)
@@ -1495,7 +1591,7 @@ class GPUModel:
                                   min_p: float, temperature: float = 1.0,
                                   top_k: int = 0, top_p: float = 1.0,
                                   proc: bool = False,
-                                  logprobs: bool = False):
+                                  logprobs: bool = False, rows=None):
         """Batched decode via (stage+quant, skinny fp8 MFMA GEMM) pairs:
         B = 3..16 lockstep rows, W streamed once per projection."""
         cfg = self.config
@@ -1582,11 +1678,8 @@ class GPUModel:
             self._lp_scan(self.bt_logits[:B], slice(0, B), proc)
         if proc:
             self._adjust_rows(B)
-        ho.sample(self.bt_logits[:B], min_p, greedy, self.seed,
-                  self.rng_ctr, self.bt_gmax, self.bt_pick, self.bt_next,
-                  self.bt_ring, self.bt_nout, self.bt_lens, bump_len=True,
-                  temperature=temperature, cnt=self.bt_cnt, batch=B,
-                  top_k=top_k, top_p=top_p, sel=self.bt_sel)
+        self._sample_batch_step(B, greedy, min_p, temperature, top_k, top_p,
+                                rows)
         if logprobs:
             self._lp_commit(self.bt_logits[:B], slice(0, B), proc,
                             self.bt_next, self.bt_nout)
@@ -1712,10 +1805,16 @@ class GPUModel:
     def prefill_row(self, b: int, ids, greedy: bool = True,
                     min_p: float = 0.1, temperature: float = 1.0,
                     top_k: int = 0, top_p: float = 1.0, processors=None,
-                    logprobs=None):
+                    logprobs=None, row_sampler=None):
         """Prefill ONE sequence into slot b (other rows untouched) and
         sample its first token — a request JOINING the lockstep group
         between decode chunks (server continuous batching).
+        ``row_sampler`` (dict of ``sampling.device_row_sampler_kwargs``:
+        ``strategy`` and its fields, optional ``seed``) replaces greedy /
+        min_p / temperature / top_k / top_p: the row's own sampler
+        settings are written to the device table (draw counter 0) for
+        ``decode_rows(row_sampler=True)``, where rows of any settings
+        share one graph; the row's stream depends on its seed only.
         ``logprobs`` (int N within 0..``device_logprobs``, or None): the
         row's own top-N for ``decode_rows(logprobs=True)``; its first
         token's record is written here.  A row without it is switched
@@ -1732,6 +1831,8 @@ class GPUModel:
         assert self.world == 1
         if P + 1 >= self.max_seq:
             raise ValueError(f"prompt {P} fills the {self.max_seq} pool")
+        if row_sampler is not None:
+            samp_words, samp_mode = self._samp_pack(row_sampler)
         self._pb = b
         done = 0
         while done < P:
@@ -1747,6 +1848,11 @@ class GPUModel:
         self.bt_lens[b:b + 1].fill_(P)
         self.bt_nout[b:b + 1].zero_()
         rb = slice(b, b + 1)
+        if row_sampler is not None:
+            self.bt_samp[b].copy_(samp_words)
+            self._samp_modes[b] = samp_mode
+        else:
+            self._samp_modes.pop(b, None)
         if logprobs is not None:
             if processors is not None:
                 self._lp_alloc(raw=True)
@@ -1764,13 +1870,20 @@ class GPUModel:
         else:
             self._proc_clear(b)
         # first token for this row only (row-sliced sampler state)
-        ho.sample(self.b_logits, min_p, greedy, self.seed, self.rng_ctr,
-                  self.bt_gmax[b:b + 1], self.bt_pick[b:b + 1],
-                  self.bt_next[b:b + 1], self.bt_ring[b:b + 1],
-                  self.bt_nout[b:b + 1], self.bt_lens[b:b + 1],
-                  bump_len=False, temperature=temperature,
-                  cnt=self.bt_cnt[b:b + 1], batch=1,
-                  top_k=top_k, top_p=top_p, sel=self.bt_sel[b:b + 1])
+        if row_sampler is not None:
+            ho.sample_rows(self.b_logits, self.bt_samp[rb], self.bt_gmax[rb],
+                           self.bt_pick[rb], self.bt_cnt[rb],
+                           self.bt_next[rb], self.bt_ring[rb],
+                           self.bt_nout[rb], self.bt_lens[rb],
+                           self.bt_sel[rb], 1, False, {samp_mode})
+        else:
+            ho.sample(self.b_logits, min_p, greedy, self.seed, self.rng_ctr,
+                      self.bt_gmax[b:b + 1], self.bt_pick[b:b + 1],
+                      self.bt_next[b:b + 1], self.bt_ring[b:b + 1],
+                      self.bt_nout[b:b + 1], self.bt_lens[b:b + 1],
+                      bump_len=False, temperature=temperature,
+                      cnt=self.bt_cnt[b:b + 1], batch=1,
+                      top_k=top_k, top_p=top_p, sel=self.bt_sel[b:b + 1])
         if logprobs is not None:
             self._lp_commit(self.b_logits, rb, processors is not None,
                             self.bt_next[rb], self.bt_nout[rb])
@@ -1796,6 +1909,13 @@ class GPUModel:
                   self.bt_pick, self.bt_cnt):
             t[dst:dst + 1].copy_(t[src:src + 1])
         self.bt_ring[dst].copy_(self.bt_ring[src])
+        if src in self._samp_modes:
+            # sampler settings, seed and draw counter travel with the
+            # row: its stream continues where it was
+            self.bt_samp[dst].copy_(self.bt_samp[src])
+            self._samp_modes[dst] = self._samp_modes[src]
+        else:
+            self._samp_modes.pop(dst, None)
         if src in self._proc_rows:
             # the row's history and settings travel with it (the 4·V-byte
             # bias row only when it has one); rows without processors
@@ -1823,9 +1943,14 @@ class GPUModel:
                     min_p: float = 0.1, temperature: float = 1.0,
                     use_graph: bool = True, top_k: int = 0,
                     top_p: float = 1.0, processors: bool = False,
-                    logprobs: bool = False):
+                    logprobs: bool = False, row_sampler: bool = False):
         """n lockstep steps for rows [0, B) (each already holding a
         sampled next token from prefill_row / a previous chunk).
+        ``row_sampler``: every row samples with its own settings from the
+        device table (rows set up by ``prefill_row(row_sampler=...)``);
+        greedy / min_p / temperature / top_k / top_p are then unused and
+        the graph is keyed on which sampler stages the rows need, not on
+        any value.
         ``processors``: run the graph variant with the logit-adjust
         stage (rows set up by ``prefill_row(processors=...)``).
         ``logprobs``: run the graph variant with the logprob stage (rows
@@ -1850,6 +1975,12 @@ class GPUModel:
             self._host_lens[b] += n
         key = ("batchc", B, greedy, min_p, temperature, top_k, top_p,
                processors) + (("logprobs",) if logprobs else ())
+        if row_sampler:
+            rows = self._row_modes(B)
+            key = ("batchr", B) + self._rows_key(rows) + (processors,
+                                                          logprobs)
+            # the step bodies take the mode set after (proc, logprobs)
+            lpx = (logprobs, rows)
         if not hasattr(self, "_bgraphs"):
             self._bgraphs = {}
         g = self._bgraphs.get(key)
@@ -1905,7 +2036,7 @@ class GPUModel:
     def capture_decode_graph(self, greedy: bool = True, min_p: float = 0.1,
                              temperature: float = 1.0, top_k: int = 0,
                              top_p: float = 1.0, processors: bool = False,
-                             logprobs: bool = False):
+                             logprobs: bool = False, rows=None):
         """Capture one decode step into a hipGraph (fixed shapes: KV pool
         is preallocated and the position is a device scalar — SURVEY §7
         'graph must be shape-stable').  ``logprobs``: the step carries the
@@ -1922,11 +2053,16 @@ class GPUModel:
         ``self._graph_error``."""
         processors = bool(processors)
         mode = (greedy, min_p, temperature, top_k, top_p, processors)
+        if rows is not None:
+            # per-row sampler: the stages the row's mode needs, no value
+            mode = ("rows",) + self._rows_key(rows) + (processors,)
         lpx = (True,) if logprobs else ()
         if logprobs:
             # the logprob stage is part of the key; N is not (device data)
             mode += ("logprobs",)
             self._lp_alloc(raw=processors)
+        if rows is not None:
+            lpx = (bool(logprobs), rows)
         if self._graph_mode == mode:
             return 0, True
         if getattr(self, "_graph_failed", False):
@@ -1966,7 +2102,7 @@ class GPUModel:
                use_graph: bool = True, first_from_logits: bool = True,
                temperature: float = 1.0, top_k: int = 0,
                top_p: float = 1.0, processors: bool = False,
-               logprobs: bool = False):
+               logprobs: bool = False, row_sampler: bool = False):
         """Generate n_tokens ids device-side; returns int32 numpy ids.
         Assumes prefill() ran (len_buf == prompt length, logits ready).
         ``processors``: run the logit-adjust stage ahead of every sample
@@ -1974,7 +2110,10 @@ class GPUModel:
         ``logprobs``: run the logprob stage around every sample with row
         0's top-N (``setup_logprobs(0, N)``; ``generate_tokens`` does it);
         read the records with ``logprob_records`` — at most LP_RING
-        tokens per call."""
+        tokens per call.
+        ``row_sampler``: sample with the settings ``generate_tokens`` wrote
+        to the single-sequence sampler table (greedy / min_p / temperature
+        / top_k / top_p are then unused)."""
         processors = bool(processors)
         if processors:
             self._proc_alloc()
@@ -1986,6 +2125,10 @@ class GPUModel:
             self._lp_alloc(raw=processors)
             self._lp_batch = False
         lpx = (True,) if logprobs else ()
+        rows = self._s_rows if row_sampler else None
+        if rows is not None:
+            # the step takes the mode set after (proc, logprobs)
+            lpx = (logprobs, rows)
         if getattr(self, "_host_len", 0) + n_tokens > self.max_seq:
             raise ValueError(
                 f"decode would overflow the KV pool: len {self._host_len} "
@@ -1998,12 +2141,18 @@ class GPUModel:
             if processors:
                 ho.logit_adjust(self.b_logits, self.p_stat, self.p_proc,
                                 self.p_bias, self.next_token, False)
-            ho.sample(self.b_logits, min_p, greedy, self.seed, self.rng_ctr,
-                      self.s_gmax, self.s_pick, self.next_token,
-                      self.out_ring, self.nout, self.len_buf,
-                      bump_len=False, temperature=temperature,
-                      cnt=self.s_cnt, top_k=top_k, top_p=top_p,
-                      sel=self.s_sel)
+            if rows is not None:
+                ho.sample_rows(self.b_logits, self.s_samp, self.s_gmax,
+                               self.s_pick, self.s_cnt, self.next_token,
+                               self.out_ring, self.nout, self.len_buf,
+                               self.s_sel, 1, False, rows)
+            else:
+                ho.sample(self.b_logits, min_p, greedy, self.seed,
+                          self.rng_ctr, self.s_gmax, self.s_pick,
+                          self.next_token, self.out_ring, self.nout,
+                          self.len_buf, bump_len=False,
+                          temperature=temperature, cnt=self.s_cnt,
+                          top_k=top_k, top_p=top_p, sel=self.s_sel)
             if logprobs:
                 self._lp_commit(self.b_logits, slice(0, 1), processors,
                                 self.next_token, self.nout)

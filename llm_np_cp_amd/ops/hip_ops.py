@@ -17,6 +17,7 @@ from __future__ import annotations
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 _LIB = None
@@ -64,6 +65,11 @@ _SIGS = {
                          [ctypes.c_void_p] * 8 +
                          [ctypes.c_int, ctypes.c_int, ctypes.c_float,
                           ctypes.c_void_p, ctypes.c_void_p],
+    "launch_sample_rows": [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                           ctypes.c_int, ctypes.c_long, ctypes.c_void_p,
+                           ctypes.c_int, ctypes.c_int] +
+                          [ctypes.c_void_p] * 7 +
+                          [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p],
     "launch_logit_adjust": [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                             ctypes.c_int] + [ctypes.c_void_p] * 4 +
                            [ctypes.c_int, ctypes.c_void_p],
@@ -412,6 +418,129 @@ def sample(logits: torch.Tensor, min_p: float, greedy: bool, seed: int,
         _ptr(ctr), _ptr(gmax), _ptr(pick), _ptr(cnt),
         _ptr(next_token), _ptr(out_ring), _ptr(nout), _ptr(len_ptr),
         1 if bump_len else 0, _stream()), "sample")
+
+
+# per-row sampler table (csrc/llm_ops.hip SAMP_*): 8 32-bit words per row
+SAMP_WORDS = 8
+SAMP_GREEDY, SAMP_MIN_P, SAMP_TOP_K, SAMP_TOP_P = 0, 1, 2, 3
+SAMP_CTR = 7  # the row's draw counter, advanced on device
+
+
+def samp_row(params, seed: int, V: int) -> np.ndarray:
+    """Pack one row of the sampler table: ``uint32[SAMP_WORDS]`` = mode,
+    1/temperature, min_p, top_k, top_p, seed lo, seed hi, draw counter 0.
+    ``params`` is a mapping with ``strategy`` and that strategy's fields
+    (``min_p`` / ``temperature`` / ``top_k`` / ``top_p``; missing ones take
+    the ``SamplingParams`` defaults).  The rules are those of
+    ``sampling.device_sampler_kwargs``: ``temperature`` and ``top_p`` >= 1
+    are the min-p mode with an empty cut, ``top_k`` is clamped to ``V``.
+    The values are device data the kernels cannot report on, so they are
+    checked here (as ``sample`` checks its arguments)."""
+    V = int(V)
+    if V <= 0:
+        raise ValueError(f"V must be positive, got {V}")
+    strategy = params.get("strategy", "min_p")
+    temperature = float(params.get("temperature", 1.0))
+    if not temperature == temperature:
+        raise ValueError("temperature must not be NaN")
+    min_p, top_k, top_p = 0.0, 0, 1.0
+    if strategy == "greedy":
+        mode = SAMP_GREEDY
+    elif strategy == "min_p":
+        mode = SAMP_MIN_P
+        min_p = float(params.get("min_p", 0.1))
+        if not 0.0 <= min_p <= 1.0:
+            raise ValueError(f"min_p must be in [0, 1], got {min_p}")
+    elif strategy == "temperature":
+        mode = SAMP_MIN_P
+    elif strategy == "top_k":
+        mode = SAMP_TOP_K
+        top_k = int(params.get("top_k", 50))
+        if top_k < 0:
+            raise ValueError(f"top_k must be >= 0, got {top_k}")
+        top_k = min(max(1, top_k), V)
+    elif strategy == "top_p":
+        top_p = float(params.get("top_p", 0.9))
+        if not 0.0 < top_p:
+            raise ValueError(f"top_p must be > 0, got {top_p}")
+        top_p = min(1.0, top_p)
+        mode = SAMP_TOP_P if top_p < 1.0 else SAMP_MIN_P
+    else:
+        raise ValueError(f"unknown sampling strategy {strategy!r}")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    row = np.zeros(SAMP_WORDS, dtype=np.uint32)
+    row[0] = mode
+    row[1:3] = np.array([1.0 / max(temperature, 1e-6), min_p],
+                        dtype=np.float32).view(np.uint32)
+    row[3] = top_k
+    row[4] = np.array([top_p], dtype=np.float32).view(np.uint32)[0]
+    row[5] = seed & 0xFFFFFFFF
+    row[6] = seed >> 32
+    return row
+
+
+def sample_rows(logits: torch.Tensor, samp: torch.Tensor,
+                gmax: torch.Tensor, pick: torch.Tensor, cnt: torch.Tensor,
+                next_token: torch.Tensor, out_ring: torch.Tensor,
+                nout: torch.Tensor, len_ptr: torch.Tensor,
+                sel: torch.Tensor | None, batch: int, bump_len: bool,
+                modes):
+    """``sample`` with every parameter read per row from ``samp`` (int32
+    [>=batch, SAMP_WORDS], rows packed by ``samp_row``): rows of different
+    strategies, temperatures and seeds share one launch sequence.  Row b's
+    noise depends on its own seed and draw counter only, never on b.
+    ``modes``: the set of modes present in rows [0, batch) — the host's
+    knowledge of the table; only the stages it needs are launched (all
+    greedy: the ``sample(greedy=True)`` launch itself; no top-k / top-p
+    row: max + pick; else max + select passes + pick, ``sel`` required).
+    Scratch (gmax / pick / cnt / sel) as for ``sample``."""
+    modes = frozenset(int(m) for m in modes)
+    if not modes or not modes <= {SAMP_GREEDY, SAMP_MIN_P, SAMP_TOP_K,
+                                  SAMP_TOP_P}:
+        raise ValueError(f"modes must be a non-empty subset of 0..3, got "
+                         f"{sorted(modes)}")
+    if batch < 1:
+        raise ValueError(f"batch must be >= 1, got {batch}")
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"logits must be fp32 or bf16, got {logits.dtype}")
+    V = logits.shape[-1]
+    if not logits.is_contiguous() or logits.numel() < batch * V:
+        raise ValueError("logits must hold `batch` contiguous rows")
+    if samp.dtype != torch.int32 or not samp.is_contiguous() \
+            or samp.shape[-1] != SAMP_WORDS \
+            or samp.numel() < batch * SAMP_WORDS:
+        raise ValueError(f"samp must be contiguous int32 "
+                         f"[>=batch, {SAMP_WORDS}]")
+    for name, t in (("gmax", gmax), ("pick", pick)):
+        if t.dtype != torch.int64 or not t.is_contiguous() \
+                or t.numel() < batch:
+            raise ValueError(f"{name} must be contiguous int64 with "
+                             f"`batch` entries")
+    for name, t in (("cnt", cnt), ("next_token", next_token),
+                    ("nout", nout), ("len_ptr", len_ptr)):
+        if t is None or t.dtype != torch.int32 or not t.is_contiguous() \
+                or t.numel() < batch:
+            raise ValueError(f"{name} must be contiguous int32 with "
+                             f"`batch` entries")
+    if out_ring.dtype != torch.int32 or not out_ring.is_contiguous() \
+            or (batch > 1 and (out_ring.dim() != 2
+                               or out_ring.shape[0] < batch)):
+        raise ValueError("out_ring must be contiguous int32, one row per "
+                         "batch row")
+    any_select = bool(modes & {SAMP_TOP_K, SAMP_TOP_P})
+    if any_select and (sel is None or sel.dtype != torch.int64
+                       or not sel.is_contiguous()
+                       or sel.numel() < batch * SAMPLE_SEL_WORDS):
+        raise ValueError(f"top_k / top_p rows need an int64 `sel` scratch "
+                         f"of {SAMPLE_SEL_WORDS} words per row")
+    lbf16 = 1 if logits.dtype == torch.bfloat16 else 0
+    ring_stride = out_ring.shape[-1] if out_ring.dim() > 1 else 0
+    _check(lib().launch_sample_rows(
+        _ptr(logits), V, lbf16, batch, ctypes.c_long(ring_stride),
+        _ptr(samp), 1 if modes - {SAMP_GREEDY} else 0,
+        1 if any_select else 0, _ptr(gmax), _ptr(pick), _ptr(cnt),
+        _ptr(next_token), _ptr(out_ring), _ptr(nout), _ptr(len_ptr),
+        1 if bump_len else 0, _ptr(sel), _stream()), "sample_rows")
 
 
 # stat word layout of the logit-adjust stage (csrc/llm_ops.hip): bit 30 =

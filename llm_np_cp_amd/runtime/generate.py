@@ -24,7 +24,8 @@ from typing import Callable, List, Optional
 import numpy as np
 
 from .sampling import (SamplingParams, active_processors,
-                       device_sampler_kwargs, sample_token)
+                       device_row_sampler_kwargs, device_sampler_kwargs,
+                       sample_token)
 
 
 @dataclass
@@ -158,16 +159,16 @@ def generate(prompt: str, tokenizer, model, max_tokens: int = 200,
     logprobs=N)``); a larger N, or any other engine, takes the
     logits-visible step loop.
 
-    Seeds: the GPU fast path's device sampler derives its stream from
-    the ENGINE seed + a device counter (baked into the captured graph),
-    so ``params.seed`` is honored on the logits-visible paths (CPU
-    oracle; logprobs requests beyond the engine's ``device_logprobs`` —
-    within it they are device-sampled like every other fast-path request,
-    so ``params.seed`` is NOT honored; strategies or logit processors the
-    engine does not list in ``device_strategies`` /
-    ``device_processors``) but not by the in-graph device
-    sampler — on an engine that advertises them that now includes
-    top-k / top-p / temperature, as it always did min-p."""
+    Seeds: ``params.seed`` is honored on the logits-visible paths (CPU
+    oracle; logprobs requests beyond the engine's ``device_logprobs``;
+    strategies or logit processors the engine does not list in
+    ``device_strategies`` / ``device_processors``) and, on an engine
+    that advertises ``device_row_sampler``, on the GPU fast path too:
+    the request's settings and seed are per-row device data
+    (``generate_tokens(..., row_sampler=...)``), and the same seed gives
+    the same tokens.  Without a seed — or on an engine without that
+    capability, e.g. under tensor parallelism — the fast path's sampler
+    derives its stream from the ENGINE seed + a device counter."""
     params = params or SamplingParams()
     rng = np.random.default_rng(params.seed)
     prompt_ids = list(tokenizer.encode(prompt))
@@ -225,12 +226,21 @@ def generate(prompt: str, tokenizer, model, max_tokens: int = 200,
         def _stop_fn(all_ids):
             return any(s in tokenizer.decode(list(all_ids)) for s in stops)
 
+        # a seeded request on an engine whose sampler reads its settings
+        # per row from device memory: the seed travels with them, and the
+        # stream is a function of it alone
+        rs_kw = {}
+        if params.seed is not None and getattr(model, "device_row_sampler",
+                                               False):
+            rs_kw["row_sampler"] = device_row_sampler_kwargs(params)
+
         ids = model.generate_tokens(
             prompt_ids, max_tokens,
             eos_id=eos_set if stop_on_eos else None, on_ids=_emit,
             stop_fn=_stop_fn if stops else None,
             **device_sampler_kwargs(params),
-            **({"logprobs": int(logprobs)} if lp_on_device else {}))
+            **({"logprobs": int(logprobs)} if lp_on_device else {}),
+            **rs_kw)
         dt = time.perf_counter() - t0
         tp = getattr(model, "last_prefill_time_s", 0.0)
         hit_eos = bool(ids) and stop_on_eos and int(ids[-1]) in eos_set

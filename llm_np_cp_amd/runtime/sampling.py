@@ -159,8 +159,9 @@ def device_sampler_kwargs(params: SamplingParams) -> dict:
     (the penalties and logit_bias of the device logit-adjust stage)
     appears only when ``has_processors(params)``; callers send such a
     request to the device only when the engine lists every active one
-    in ``device_processors``.  (``seed`` has no device counterpart —
-    callers keep such requests on the host path.)"""
+    in ``device_processors``.  (``seed`` is not part of this keyword
+    set: it travels in ``device_row_sampler_kwargs``, to engines that
+    advertise ``device_row_sampler``.)"""
     kw = dict(greedy=params.strategy == "greedy", min_p=params.min_p,
               temperature=params.temperature)
     if has_processors(params):
@@ -180,6 +181,35 @@ def device_sampler_kwargs(params: SamplingParams) -> dict:
             raise ValueError(f"top_p must be > 0, got {params.top_p}")
         kw["top_p"] = min(1.0, float(params.top_p))
     elif params.strategy != "temperature":
+        raise ValueError(f"unknown sampling strategy {params.strategy!r}")
+    return kw
+
+
+def device_row_sampler_kwargs(params: SamplingParams) -> dict:
+    """The ``row_sampler`` dict of engines that advertise
+    ``device_row_sampler`` (``generate_tokens`` / ``prefill_row``): the
+    request's own sampler settings as per-row device data, drawing from
+    the distribution ``filter_probs`` defines for ``params``.  Same rules
+    as ``device_sampler_kwargs``: ``temperature`` and ``top_p`` >= 1 are a
+    min-p cut with ``min_p = 0`` (the whole vocabulary stays), ``top_k``
+    is at least 1 (the engine clamps it to the vocabulary).  ``seed`` is
+    the request's seed (None: the engine derives one per request)."""
+    kw = dict(strategy=params.strategy,
+              temperature=float(params.temperature), seed=params.seed)
+    if params.strategy == "min_p":
+        kw["min_p"] = float(params.min_p)
+    elif params.strategy == "top_k":
+        kw["top_k"] = max(1, int(params.top_k))
+    elif params.strategy == "top_p":
+        if not 0.0 < params.top_p:
+            raise ValueError(f"top_p must be > 0, got {params.top_p}")
+        if params.top_p >= 1.0:
+            kw.update(strategy="min_p", min_p=0.0)
+        else:
+            kw["top_p"] = float(params.top_p)
+    elif params.strategy == "temperature":
+        kw.update(strategy="min_p", min_p=0.0)
+    elif params.strategy != "greedy":
         raise ValueError(f"unknown sampling strategy {params.strategy!r}")
     return kw
 

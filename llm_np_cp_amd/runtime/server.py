@@ -17,7 +17,10 @@ sampling strategies the engine's device sampler does not implement
 (``device_strategies``; top_k/top_p/temperature on engines without the
 selection stage), with penalties / ``logit_bias`` on an engine that does
 not list them in ``device_processors``, or a non-batch engine fall back
-to single-sequence generate().
+to single-sequence generate().  On an engine that advertises
+``device_row_sampler`` the sampler's settings and the request's seed are
+per-row device data: requests with different strategies / temperatures /
+filter values share one group and one captured graph.
 
     python -m llm_np_cp_amd.runtime.server --model llama-3.2-1b \
         --port 8080 --max-batch 8
@@ -151,8 +154,13 @@ class BatchScheduler:
     def __init__(self, generate_one, run_group, max_batch: int,
                  window_s: float = 0.004,
                  device_strategies=("greedy", "min_p"),
-                 device_processors=(), device_logprobs: int = 0):
+                 device_processors=(), device_logprobs: int = 0,
+                 device_row_sampler: bool = False):
         self.generate_one = generate_one
+        # run_group's engine samples every row with its own strategy /
+        # temperature / filter / seed (per-row device data): sampler
+        # settings then no longer split groups
+        self.device_row_sampler = bool(device_row_sampler)
         # largest top-N run_group's engine reports on device, per row —
         # logprobs requests within it may join a group (0: none may)
         self.device_logprobs = int(device_logprobs or 0)
@@ -185,8 +193,12 @@ class BatchScheduler:
         self.q.put(p)
         return p
 
-    @staticmethod
-    def _key(req):
+    def _key(self, req):
+        if self.device_row_sampler:
+            # sampler settings are per-row device data too: what is left
+            # is what shapes the group's host loop and its graph
+            return (req.stop_on_eos, bool(_req_processors(req)),
+                    getattr(req, "logprobs", None) is not None)
         return (req.strategy, round(req.min_p, 6),
                 round(req.temperature, 6), req.stop_on_eos,
                 getattr(req, "top_k", 50),
@@ -316,7 +328,7 @@ def build_app(model_name: str = "llama-3.2-1b", backend: str = "auto",
 
     import llm_np_cp_amd as L
     from .generate import logprob_entries
-    from .sampling import device_sampler_kwargs
+    from .sampling import device_row_sampler_kwargs, device_sampler_kwargs
 
     tok, model, cfg = L.load_model(model_name, backend=backend,
                                    dtype=dtype, max_seq=max_seq,
@@ -329,6 +341,9 @@ def build_app(model_name: str = "llama-3.2-1b", backend: str = "auto",
         # GPU engines built with batch pools serve the lockstep group
         can_batch = (max_batch > 1
                      and type(model).__name__ == "GPUModel")
+    # the engine's sampler reads each row's own settings + seed from
+    # device memory: mixed sampler settings share one lockstep group
+    row_sampler = bool(getattr(model, "device_row_sampler", False))
 
     eos = getattr(cfg, "eos_token_id", None)
     eos_set = (set() if eos is None else {int(eos)}
@@ -439,16 +454,23 @@ def build_app(model_name: str = "llama-3.2-1b", backend: str = "auto",
             return
         r0 = pendings[0].req
         stop_eos = r0.stop_on_eos
-        # one sampler setting per group (_key keeps groups homogeneous)
-        skw = device_sampler_kwargs(L.SamplingParams(
-            strategy=r0.strategy, min_p=r0.min_p,
-            temperature=r0.temperature,
-            top_k=getattr(r0, "top_k", 50),
-            top_p=getattr(r0, "top_p", 0.9)))
+        if row_sampler:
+            # each row brings its OWN sampler settings and seed (device
+            # data): nothing of them is shared by the group
+            skw = {}
+        else:
+            # one sampler setting per group (_key keeps groups homogeneous)
+            skw = device_sampler_kwargs(L.SamplingParams(
+                strategy=r0.strategy, min_p=r0.min_p,
+                temperature=r0.temperature,
+                top_k=getattr(r0, "top_k", 50),
+                top_p=getattr(r0, "top_p", 0.9)))
         # a processors group (_key): each row brings its OWN penalties /
         # bias (device data), the decode graph just carries the stage
         with_proc = bool(_req_processors(r0))
         dkw = dict(skw, processors=True) if with_proc else skw
+        if row_sampler:
+            dkw = dict(dkw, row_sampler=True)
         # a logprobs group (_key): each row brings its OWN top-N (device
         # data); its records are gathered chunk by chunk
         with_lp = getattr(r0, "logprobs", None) is not None
@@ -472,6 +494,17 @@ def build_app(model_name: str = "llama-3.2-1b", backend: str = "auto",
                     return
             if with_lp:
                 pkw = dict(pkw, logprobs=int(p.req.logprobs))
+            if row_sampler:
+                try:
+                    pkw = dict(pkw, row_sampler=device_row_sampler_kwargs(
+                        _sampling_params(p.req,
+                                         getattr(p.req, "seed", None))))
+                except (TypeError, ValueError) as e:
+                    # bad sampler values fail this request alone
+                    stats["requests"] += 1
+                    p.error = e
+                    p.done.set()
+                    return
             model.prefill_row(slot, tok.encode(p.req.prompt), **pkw)
             p.prefill_s = time.time() - t_p
             rows.append(_Row(p))
@@ -566,7 +599,8 @@ def build_app(model_name: str = "llama-3.2-1b", backend: str = "auto",
                            device_processors=getattr(
                                model, "device_processors", ()),
                            device_logprobs=getattr(
-                               model, "device_logprobs", 0))
+                               model, "device_logprobs", 0),
+                           device_row_sampler=row_sampler)
     app = FastAPI(title="llm_np_cp_amd", version=L.__version__)
     app.state.scheduler = sched  # in-process callers (and tests) queue here
 
