@@ -1900,21 +1900,23 @@ k_attn_t(const u16* __restrict__ q, const void* __restrict__ kc,
 // Gemma-2 semantics included: sliding window + attn-logit softcap.
 // ====================================================================
 
+// The attention block's body, shared by the plain and the prefetching
+// kernel: `chunk` of `SPLIT` for head blockIdx.x of row blockIdx.z.
 template <bool KV8>
-__global__ void __launch_bounds__(256)
-k_attn_dec_t(const u16* __restrict__ qkv, void* __restrict__ kc,
-             void* __restrict__ vc, u16* __restrict__ out,
-             const int* __restrict__ len_ptr, const float* __restrict__ cost,
-             const float* __restrict__ sint, float* __restrict__ kS,
-             float* __restrict__ vS, float* __restrict__ scratch,
-             int* __restrict__ cnt, int nh, int kvh, int hd, int S,
-             float scale, float softcap, int window) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+DEVINL void attn_dec_body(char* smem, const int chunk, const int SPLIT,
+                          const u16* __restrict__ qkv, void* __restrict__ kc,
+                          void* __restrict__ vc, u16* __restrict__ out,
+                          const int* __restrict__ len_ptr,
+                          const float* __restrict__ cost,
+                          const float* __restrict__ sint,
+                          float* __restrict__ kS, float* __restrict__ vS,
+                          float* __restrict__ scratch, int* __restrict__ cnt,
+                          int nh, int kvh, int hd, int S, float scale,
+                          float softcap, int window) {
   float* red = (float*)smem;              // [4][hd] + [4][2] + flag
   int* lastflag = (int*)(red + 4 * hd + 8);
 
   const int h = blockIdx.x;
-  const int chunk = blockIdx.y, SPLIT = gridDim.y;
   // batch axis (lockstep sequences): per-b qkv/out rows, KV pool,
   // scales, merge scratch and tickets; the position is shared
   const int b = blockIdx.z;
@@ -2243,6 +2245,188 @@ k_attn_dec_t(const u16* __restrict__ qkv, void* __restrict__ kc,
   if (threadIdx.x == 0) cnt[h] = 0;  // re-arm for the next graph replay
 }
 
+// --------------------------------------------------------------------
+// Weight prefetch from the attention launch.  The attention blocks are
+// a latency chain that leaves HBM idle, and the next two kernels'
+// weights are known at capture time, so the prefetching kernel variant
+// carries extra grid.y rows of blocks that pull up to four byte regions
+// through L2 into the Infinity Cache with plain (retaining) loads.
+// They synchronise with nothing and touch no attention state (no cnt,
+// no scratch, no LDS); the only store is guarded by `never` (always -1)
+// and exists to keep the loads alive.
+// --------------------------------------------------------------------
+
+struct AttnPf {
+  const void* ptr[4];
+  long bytes[4];   // rounded DOWN to whole 16 B; 0 or a null ptr skips
+  long stride0;    // region 0: bytes one consumer block reads (0 = flat)
+  float* sink;
+  int never;       // -1: no thread index equals it
+};
+
+constexpr int PF_LD = 8;              // independent 16-B loads per lane
+constexpr int PF_TRIP = 256 * PF_LD;  // 16-B segments per block trip
+
+// One trip: PF_LD loads per lane, each wave-load 1 KB contiguous.  `seg`
+// maps a trip-relative segment number to a segment of the region and is
+// clamped here to [0, nseg): no load starts at or beyond ptr + bytes.
+template <typename F>
+DEVINL uint32_t attn_pf_trip(const u4v* __restrict__ base, long nseg, F seg) {
+  u4v v[PF_LD];
+#pragma unroll
+  for (int j = 0; j < PF_LD; j++) {
+    long s = seg(j * 256 + (int)threadIdx.x);
+    s = s < nseg ? s : nseg - 1;
+    v[j] = base[s];
+  }
+  uint32_t a = 0;
+#pragma unroll
+  for (int j = 0; j < PF_LD; j++) {
+    // pin all 16 B: with only word 0 live the compiler narrows the load
+    // to a dword (measured the same; the wide form is the stated one)
+    asm volatile("" ::"v"(v[j]));
+    a ^= v[j][0];  // one live word per load
+  }
+  return a;
+}
+
+DEVINL void attn_dec_prefetch(const AttnPf& pf, const int split) {
+  const uint32_t nx = gridDim.x;
+  const uint32_t pfy = gridDim.y - split;
+  const uint32_t npb = nx * pfy * gridDim.z;  // prefetch blocks in all
+  const uint32_t pb =
+      (blockIdx.z * pfy + (blockIdx.y - split)) * nx + blockIdx.x;
+  uint32_t acc = 0;
+  // The regions form one range, concatenated in whole trips and dealt
+  // to the blocks round-robin: `g0` = trips handed out so far, mod npb.
+  uint32_t g0 = 0;
+#pragma unroll
+  for (int r = 0; r < 4; r++) {
+    const u4v* base = (const u4v*)pf.ptr[r];
+    const long nseg = pf.bytes[r] >> 4;
+    if (base == nullptr || nseg <= 0) continue;
+    const long spu = pf.stride0 >> 4;  // segments per consumer block
+    if (r == 0 && spu > 0 && (nx & 7) == 0 && nseg < (1l << 31)) {
+      // L2 placement (speed only; nothing depends on it): workgroups
+      // are dealt round-robin to the 8 XCDs, so with nx % 8 == 0 this
+      // block shares an XCD with the consumer blocks u = c (mod 8).
+      // The blocks of class c walk those units as one virtual range.
+      const uint32_t c = blockIdx.x & 7;
+      const uint32_t nunit = (uint32_t)((nseg + spu - 1) / spu);
+      if (nunit <= c) continue;
+      const uint32_t uspu = (uint32_t)spu;
+      const long vseg = (long)((nunit - c + 7) / 8) * spu;
+      const uint32_t rc = (pb / nx) * (nx / 8) + blockIdx.x / 8;
+      for (long t = rc; t * PF_TRIP < vseg; t += npb / 8) {
+        acc ^= attn_pf_trip(base, nseg, [&](int i) {
+          long v = t * PF_TRIP + i;
+          v = v < vseg ? v : vseg - 1;
+          const uint32_t k = (uint32_t)v / uspu;
+          return (long)(c + 8 * k) * spu + ((uint32_t)v - k * uspu);
+        });
+      }
+      continue;
+    }
+    const long ntrip = (nseg + PF_TRIP - 1) / PF_TRIP;
+    for (long t = (pb + npb - g0) % npb; t < ntrip; t += npb)
+      acc ^= attn_pf_trip(base, nseg,
+                          [&](int i) { return t * PF_TRIP + i; });
+    g0 = (uint32_t)((g0 + ntrip) % npb);
+  }
+  // the fold above needs every load's data, so this also waits for them
+  asm volatile("" ::"v"(acc));
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if ((int)threadIdx.x == pf.never) pf.sink[pb & 255] = (float)acc;
+}
+
+// PF: grid (nh, split + PFY, batch); rows y >= split are prefetch blocks
+// (dispatched behind the attention blocks of their batch row), so the
+// attention chunking takes `split` from the argument.  The plain kernel
+// has no such arguments (PFA is empty: its argument list is the one it
+// always had) and chunks by gridDim.y.
+struct AttnPfLaunch {
+  int split;
+  AttnPf pf;
+};
+
+template <bool KV8, bool PF, typename... PFA>
+__global__ void __launch_bounds__(256)
+k_attn_dec_t(const u16* __restrict__ qkv, void* __restrict__ kc,
+             void* __restrict__ vc, u16* __restrict__ out,
+             const int* __restrict__ len_ptr, const float* __restrict__ cost,
+             const float* __restrict__ sint, float* __restrict__ kS,
+             float* __restrict__ vS, float* __restrict__ scratch,
+             int* __restrict__ cnt, int nh, int kvh, int hd, int S,
+             float scale, float softcap, int window, PFA... pfa) {
+  static_assert(sizeof...(PFA) == (PF ? 1 : 0), "PF takes one AttnPfLaunch");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  int SPLIT = gridDim.y;
+  if constexpr (PF) {
+    const AttnPfLaunch& a = (pfa, ...);
+    if ((int)blockIdx.y >= a.split) {
+      attn_dec_prefetch(a.pf, a.split);
+      return;
+    }
+    SPLIT = a.split;
+  }
+  attn_dec_body<KV8>(smem, blockIdx.y, SPLIT, qkv, kc, vc, out, len_ptr, cost,
+                     sint, kS, vS, scratch, cnt, nh, kvh, hd, S, scale,
+                     softcap, window);
+}
+
+// Launches the attention kernel with `pf_blocks` prefetch blocks (rounded
+// to whole grid.y rows of nh blocks) over up to four regions; stride0 is
+// "rows per consumer block x row bytes" of region 0's consumer, 0 to walk
+// it flat.  pf_blocks == 0 dispatches the plain kernel.
+static hipError_t attn_dec_launch(const void* qkv, void* kc, void* vc,
+                                  void* out, const void* len_ptr,
+                                  const void* cost, const void* sint,
+                                  void* kS, void* vS, int kv8, void* scratch,
+                                  void* cnt, int split, int batch, int nh,
+                                  int kvh, int hd, int S, float scale,
+                                  float softcap, int window, int pf_blocks,
+                                  const AttnPf& pf, hipStream_t stream) {
+  size_t lds = (4 * hd + 8) * sizeof(float) + 16;
+  const int pfy = pf_blocks > 0 ? (pf_blocks + nh - 1) / nh : 0;
+#define ATTN_DEC_ARGS                                                        \
+  (const u16*)qkv, kc, vc, (u16*)out, (const int*)len_ptr,                   \
+      (const float*)cost, (const float*)sint, (float*)kS, (float*)vS,        \
+      (float*)scratch, (int*)cnt, nh, kvh, hd, S, scale, softcap, window
+#define ATTN_DEC_CASE(KV8V)                                                  \
+  hipLaunchKernelGGL((k_attn_dec_t<KV8V, false>), dim3(nh, split, batch),    \
+                     dim3(256), lds, stream, ATTN_DEC_ARGS)
+#define ATTN_DEC_PF_CASE(KV8V)                                               \
+  hipLaunchKernelGGL((k_attn_dec_t<KV8V, true, AttnPfLaunch>),               \
+                     dim3(nh, split + pfy, batch), dim3(256), lds, stream,   \
+                     ATTN_DEC_ARGS, AttnPfLaunch{split, pf})
+  if (pfy > 0) {
+    if (kv8) ATTN_DEC_PF_CASE(true);
+    else ATTN_DEC_PF_CASE(false);
+  } else {
+    if (kv8) ATTN_DEC_CASE(true);
+    else ATTN_DEC_CASE(false);
+  }
+#undef ATTN_DEC_PF_CASE
+#undef ATTN_DEC_ARGS
+#undef ATTN_DEC_CASE
+  return hipGetLastError();
+}
+
+extern "C" hipError_t launch_attn_dec_pf(
+    const void* qkv, void* kc, void* vc, void* out, const void* len_ptr,
+    const void* cost, const void* sint, void* kS, void* vS, int kv8,
+    void* scratch, void* cnt, int split, int batch, int nh, int kvh, int hd,
+    int S, float scale, float softcap, int window, int pf_blocks,
+    const void* p0, long n0, const void* p1, long n1, const void* p2,
+    long n2, const void* p3, long n3, long stride0, void* sink,
+    hipStream_t stream) {
+  AttnPf pf{{p0, p1, p2, p3}, {n0, n1, n2, n3}, stride0, (float*)sink, -1};
+  if (pf_blocks > 0 && sink == nullptr) return hipErrorInvalidValue;
+  return attn_dec_launch(qkv, kc, vc, out, len_ptr, cost, sint, kS, vS, kv8,
+                         scratch, cnt, split, batch, nh, kvh, hd, S, scale,
+                         softcap, window, pf_blocks, pf, stream);
+}
+
 extern "C" hipError_t launch_attn_dec(const void* qkv, void* kc, void* vc,
                                       void* out, const void* len_ptr,
                                       const void* cost, const void* sint,
@@ -2252,19 +2436,9 @@ extern "C" hipError_t launch_attn_dec(const void* qkv, void* kc, void* vc,
                                       int nh, int kvh, int hd, int S,
                                       float scale, float softcap, int window,
                                       hipStream_t stream) {
-  size_t lds = (4 * hd + 8) * sizeof(float) + 16;
-#define ATTN_DEC_CASE(KV8V)                                                  \
-  hipLaunchKernelGGL((k_attn_dec_t<KV8V>), dim3(nh, split, batch),          \
-                     dim3(256), lds,                                        \
-                     stream, (const u16*)qkv, kc, vc, (u16*)out,            \
-                     (const int*)len_ptr, (const float*)cost,               \
-                     (const float*)sint, (float*)kS, (float*)vS,            \
-                     (float*)scratch, (int*)cnt, nh, kvh, hd, S, scale,     \
-                     softcap, window)
-  if (kv8) ATTN_DEC_CASE(true);
-  else ATTN_DEC_CASE(false);
-#undef ATTN_DEC_CASE
-  return hipGetLastError();
+  return attn_dec_launch(qkv, kc, vc, out, len_ptr, cost, sint, kS, vS, kv8,
+                         scratch, cnt, split, batch, nh, kvh, hd, S, scale,
+                         softcap, window, 0, AttnPf{}, stream);
 }
 
 // ====================================================================
@@ -4207,31 +4381,6 @@ extern "C" hipError_t launch_gemm_fp4w(const void* X, const void* W4,
                        dim3(256), 0, stream, (const float*)accbuf,
                        (const u16*)res, (u16*)Y, total);
   }
-  return hipGetLastError();
-}
-
-// ====================================================================
-// Weight prefetcher (side-stream): stream a tensor through L2/MALL with
-// plain (retaining) loads so the 256 MB Infinity Cache holds the NEXT
-// layer's weights before its compute kernel issues.  The sink write
-// keeps the loads alive; modest grid so compute keeps its CUs.
-// ====================================================================
-
-extern "C" __global__ void __launch_bounds__(256)
-k_prefetch(const u16* __restrict__ p, long n, float* __restrict__ sink) {
-  float acc = 0.f;
-  for (long i = ((long)blockIdx.x * 256 + threadIdx.x) * 8; i < n;
-       i += (long)gridDim.x * 256 * 8) {
-    s8v v = *(const s8v*)(p + i);
-    acc += b2f(((u16*)&v)[0]);  // one live use per 16 B line segment
-  }
-  if (acc == 1e30f) sink[blockIdx.x] = acc;  // never true; keeps loads
-}
-
-extern "C" hipError_t launch_prefetch(const void* p, long n_elems,
-                                      void* sink, hipStream_t stream) {
-  hipLaunchKernelGGL(k_prefetch, dim3(128), dim3(256), 0, stream,
-                     (const u16*)p, n_elems, (float*)sink);
   return hipGetLastError();
 }
 

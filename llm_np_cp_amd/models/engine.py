@@ -178,16 +178,43 @@ class GPUModel:
         self._alloc_state(prefill_chunk)
         self._graph = None
         self._graph_mode = None
-        # side-stream weight prefetcher — measured NEGATIVE (the fork's
-        # join makes the sequential prefetch chain the critical path:
-        # fp8 1391 -> 764 tok/s), so off by default; LLM_PREFETCH=1 to
-        # experiment
+        self._plan_attn_pf()
+
+    def _plan_attn_pf(self):
+        """Weight prefetch carried by the decode attention launch
+        (`ho.attn_dec_pf`): per-layer regions, computed once here.
+        LLM_ATTN_PF = byte budget per layer, 0 = off, default `auto`
+        (o_proj's matrix when it fits the attention window, see
+        `attn_prefetch.default_budget`); LLM_ATTN_PF_BLOCKS = prefetch
+        blocks per launch (default 4 grid rows of nh).  Measured in
+        profiles/attn_prefetch.md."""
         import os as _os
-        self.prefetch_on = _os.environ.get("LLM_PREFETCH", "0") == "1"
-        self._pf_stream = torch.cuda.Stream(device=self.device)
-        self._pf_sink = torch.zeros(256, dtype=torch.float32,
-                                    device=self.device)
-        self._pf_events = []
+        from .attn_prefetch import (consumer_stride, default_budget,
+                                    plan_attn_prefetch)
+        self._attn_pf = None
+        _b = _os.environ.get("LLM_ATTN_PF", "auto").strip().lower()
+        if _b in ("", "0") or self.moe:
+            return
+        sfx = "_q4" if self.wq4 else "_q" if self.fp8 else ""
+        plans = []
+        for lw in self.layers:
+            wo, wgu = lw["wo" + sfx], lw["wgu" + sfx]
+            nb = {"wo": wo.numel() * wo.element_size(),
+                  "wgu": wgu.numel() * wgu.element_size()}
+            budget = (default_budget(nb["wo"], nb["wgu"]) if _b == "auto"
+                      else int(_b))
+            base = {"wo": wo.data_ptr(), "wgu": wgu.data_ptr()}
+            plans.append([(base[n] + off, size) for n, off, size in
+                          plan_attn_prefetch(nb["wo"], nb["wgu"],
+                                             self.inter_l, self.H, budget)])
+            # o_proj block b owns 4 consecutive rows of wo
+            self.attn_pf_stride = consumer_stride(nb["wo"], self.H, 4)
+        _n = _os.environ.get("LLM_ATTN_PF_BLOCKS")
+        self.attn_pf_blocks = int(_n) if _n else 4 * self.nh_l
+        if self.attn_pf_blocks > 0 and any(plans):
+            self._attn_pf = plans
+            self._pf_sink = torch.zeros(256, dtype=torch.float32,
+                                        device=self.device)
 
     # ------------------------------------------------------------------
     def _auto_max_seq(self) -> int:
@@ -1265,14 +1292,6 @@ class GPUModel:
         else:
             ho.gemv(lw[name], x, y, **kw)
 
-    def _pf_tensors(self, lw):
-        if self.wq4:
-            return (lw["wqkv_q4"], lw["wo_q4"], lw["wgu_q4"],
-                    lw["wdown_q4"])
-        if self.fp8:
-            return (lw["wqkv_q"], lw["wo_q"], lw["wgu_q"], lw["wdown_q"])
-        return (lw["wqkv"], lw["wo"], lw["wgu"], lw["wdown"])
-
     def _decode_step(self, greedy: bool, min_p: float,
                      temperature: float = 1.0, top_k: int = 0,
                      top_p: float = 1.0, proc: bool = False,
@@ -1282,8 +1301,9 @@ class GPUModel:
         inside the attention kernel.  bf16 weights: the gate+up GEMV
         computes the GLU itself (paired rows) and the down projection
         reads the I-long activation directly; fp8 / MXFP4 weights: the
-        GLU is the down projection's staging pre-op.  The side-stream
-        weight prefetcher (`prefetch_on`) is off unless asked for."""
+        GLU is the down projection's staging pre-op.  With LLM_ATTN_PF
+        set, the attention launch also prefetches the layer's o_proj and
+        gate+up weights (`_plan_attn_pf`)."""
         cfg = self.config
         eps = cfg.rms_norm_eps
         if self.fp8 or self.wq4:
@@ -1297,19 +1317,8 @@ class GPUModel:
         hnext = self.b_hb
         t1 = self.b_t1[0]
         t2 = self.b_t2
-        s0 = torch.cuda.current_stream()
-        pf = self.prefetch_on
-        self._pf_events = []
         prev = None  # previous gemma layer (its postffn norm fused here)
         for i, lw in enumerate(self.layers):
-            if pf and i + 1 < len(self.layers):
-                ev = torch.cuda.Event()
-                ev.record(s0)
-                self._pf_events.append(ev)
-                self._pf_stream.wait_event(ev)
-                with torch.cuda.stream(self._pf_stream):
-                    for t in self._pf_tensors(self.layers[i + 1]):
-                        ho.prefetch(t, self._pf_sink)
             window = cfg.sliding_window if cfg.is_sliding(i) else 0
             if self.gemma and prev is not None:
                 # h' = h + norm(t2_prev)*g_postffn_prev; stage norm(h')*g_in
@@ -1332,13 +1341,21 @@ class GPUModel:
                 self._dgemv(lw, "wqkv", h, self.b_qkv, stage=ho.STAGE_NORM,
                             g=lw["g_in"], res=lw.get("bqkv"), eps=eps)
             prev = lw
-            ho.attn_dec(self.b_qkv, self.k_cache[i], self.v_cache[i],
-                        self.b_att[0], self.len_buf, self.cos_t, self.sin_t,
-                        self.attn_scratch, self.attn_cnt,
-                        self.nh_l, self.kvh_l, self.hd, self.scale,
-                        softcap=self.attn_softcap, window=window or 0,
-                        split=self.attn_split,
-                        kS=self.k_scale[i], vS=self.v_scale[i])
+            pfkw = {}
+            attn_dec = ho.attn_dec
+            if self._attn_pf is not None and self._attn_pf[i]:
+                attn_dec = ho.attn_dec_pf
+                pfkw = dict(regions=self._attn_pf[i],
+                            pf_blocks=self.attn_pf_blocks,
+                            stride0=self.attn_pf_stride,
+                            sink=self._pf_sink)
+            attn_dec(self.b_qkv, self.k_cache[i], self.v_cache[i],
+                     self.b_att[0], self.len_buf, self.cos_t, self.sin_t,
+                     self.attn_scratch, self.attn_cnt,
+                     self.nh_l, self.kvh_l, self.hd, self.scale,
+                     softcap=self.attn_softcap, window=window or 0,
+                     split=self.attn_split,
+                     kS=self.k_scale[i], vS=self.v_scale[i], **pfkw)
             if self.gemma:
                 self._dgemv(lw, "wo", self.b_att[0], t1)
                 tpu.all_reduce(t1)
@@ -1400,11 +1417,6 @@ class GPUModel:
                 else:
                     self._dgemv(lw, "wdown", self.b_gu[:self.inter_l], h,
                                 res=h, **downkw)
-        if pf:
-            ev = torch.cuda.Event()
-            ev.record(self._pf_stream)
-            self._pf_events.append(ev)
-            s0.wait_event(ev)  # join the fork before the step ends
         if self.gemma:
             # last layer's post-ffn sandwich norm + final norm, both
             # fused into the lm_head staging (NORM2: h' = h + norm(t2)*

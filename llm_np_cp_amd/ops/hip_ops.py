@@ -50,6 +50,12 @@ _SIGS = {
                        [ctypes.c_void_p] * 2 + [ctypes.c_int] * 6 +
                        [ctypes.c_float, ctypes.c_float, ctypes.c_int,
                         ctypes.c_void_p],
+    "launch_attn_dec_pf": [ctypes.c_void_p] * 9 + [ctypes.c_int] +
+                          [ctypes.c_void_p] * 2 + [ctypes.c_int] * 6 +
+                          [ctypes.c_float, ctypes.c_float, ctypes.c_int,
+                           ctypes.c_int] +
+                          [ctypes.c_void_p, ctypes.c_long] * 4 +
+                          [ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p],
     "launch_glu": [ctypes.c_void_p] * 3 + [ctypes.c_long, ctypes.c_int,
                                            ctypes.c_void_p],
     "launch_embed": [ctypes.c_void_p] * 3 + [ctypes.c_int] * 2 +
@@ -82,8 +88,6 @@ _SIGS = {
                               ctypes.c_int] + [ctypes.c_void_p] * 8,
     "launch_gemm_bf16": [ctypes.c_void_p] * 5 + [ctypes.c_int] * 3 +
                         [ctypes.c_void_p],
-    "launch_prefetch": [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p,
-                        ctypes.c_void_p],
     "launch_softcap": [ctypes.c_void_p, ctypes.c_long, ctypes.c_float,
                        ctypes.c_void_p],
     "launch_addinto": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long,
@@ -325,6 +329,42 @@ def attn_dec(qkv: torch.Tensor, k_cache: torch.Tensor,
         _ptr(scratch), _ptr(cnt), split, batch,
         nh, kvh, hd, S, ctypes.c_float(scale),
         ctypes.c_float(softcap), window, _stream()), "attn_dec")
+
+
+def attn_dec_pf(qkv: torch.Tensor, k_cache: torch.Tensor,
+                v_cache: torch.Tensor, out: torch.Tensor,
+                len_ptr: torch.Tensor, cos_t: torch.Tensor,
+                sin_t: torch.Tensor, scratch: torch.Tensor,
+                cnt: torch.Tensor, nh: int, kvh: int, hd: int,
+                scale: float, softcap: float = 0.0, window: int = 0,
+                split: int = 1, kS: torch.Tensor | None = None,
+                vS: torch.Tensor | None = None, batch: int = 1, *,
+                regions=(), pf_blocks: int = 0, stride0: int = 0,
+                sink: torch.Tensor | None = None):
+    """`attn_dec` whose launch also carries `pf_blocks` prefetch blocks
+    (rounded up to whole grid rows of `nh`): they pull up to four
+    `regions`, (device address, bytes) pairs, into the cache hierarchy
+    while the attention blocks wait on their latency chain, and write
+    nothing.  `stride0`: bytes one consumer block reads of region 0 (L2
+    placement heuristic; 0 = flat walk).  `sink`: >= 256 fp32, never
+    written.  pf_blocks == 0 launches the plain kernel."""
+    S = k_cache.shape[-2]
+    regions = list(regions)
+    assert len(regions) <= 4
+    if pf_blocks > 0:
+        assert sink is not None and sink.numel() >= 256
+    flat = []
+    for addr, nbytes in regions + [(0, 0)] * (4 - len(regions)):
+        assert addr % 16 == 0 and nbytes >= 0
+        flat += [addr, nbytes]
+    _check(lib().launch_attn_dec_pf(
+        _ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(out), _ptr(len_ptr),
+        _ptr(cos_t), _ptr(sin_t), _ptr(kS), _ptr(vS),
+        1 if kS is not None else 0,
+        _ptr(scratch), _ptr(cnt), split, batch,
+        nh, kvh, hd, S, ctypes.c_float(scale),
+        ctypes.c_float(softcap), window, pf_blocks, *flat, stride0,
+        _ptr(sink), _stream()), "attn_dec_pf")
 
 
 def glu(gate: torch.Tensor, up: torch.Tensor, out: torch.Tensor, act: int):
@@ -857,13 +897,6 @@ def gemm_fp4w(X: torch.Tensor, Wq4: torch.Tensor, We4: torch.Tensor,
     _check(lib().launch_gemm_fp4w(
         _ptr(X), _ptr(Wq4), _ptr(We4), _ptr(Y), _ptr(res), _ptr(accbuf),
         M, N, K, _stream()), "gemm_fp4w")
-
-
-def prefetch(t: torch.Tensor, sink: torch.Tensor):
-    """Stream t through the cache hierarchy (side-stream warmer)."""
-    n = t.numel() * t.element_size() // 2  # treat as u16 elements
-    _check(lib().launch_prefetch(_ptr(t), n, _ptr(sink), _stream()),
-           "prefetch")
 
 
 def softcap(y: torch.Tensor, cap: float):
