@@ -21,6 +21,7 @@ spec in SURVEY §2.4 rather than translated.
 
 from __future__ import annotations
 
+from functools import partial
 from typing import Dict, Optional
 
 import numpy as np
@@ -30,6 +31,7 @@ from ..core.config import ModelConfig
 from ..ops import hip_ops as ho
 from ..parallel import tp as tpu
 from ..utils.tracing import trace_range
+from .decode_spec import RowState, SampleSpec
 
 
 class DeviceCacheHandle:
@@ -135,6 +137,11 @@ class GPUModel:
         self._req_serial = 0
         # mode set of the single-sequence table row (all zero = greedy)
         self._s_rows = frozenset({0})
+        # host mirrors of len_buf / bt_lens (overflow guards) and the
+        # number of lockstep rows in use
+        self._host_len = 0
+        self._host_lens = [0] * max_batch
+        self._batch_n = 0
         if device is None:
             device = f"cuda:{self.rank % max(torch.cuda.device_count(), 1)}"
         self.device = torch.device(device)
@@ -176,8 +183,13 @@ class GPUModel:
             max_seq = self._auto_max_seq()
         self.max_seq = max_seq
         self._alloc_state(prefill_chunk)
+        # single-slot graph of decode / decode_batch, per-key graphs of
+        # decode_rows; a failed capture switches capturing off for good
         self._graph = None
         self._graph_mode = None
+        self._bgraphs = {}
+        self._graph_failed = False
+        self._graph_error = None
         self._plan_attn_pf()
 
     def _plan_attn_pf(self):
@@ -504,6 +516,10 @@ class GPUModel:
         # per-row sampler table (mode, 1/T, min_p, top_k, top_p, seed,
         # draw counter) of the single-sequence path
         self.s_samp = torch.zeros(1, ho.SAMP_WORDS, **i32)
+        # what the sampling tail works on: the single sequence's state ...
+        self._sv = RowState(self.s_samp, self.s_gmax, self.s_pick,
+                            self.s_cnt, self.s_sel, self.next_token,
+                            self.out_ring, self.nout, self.len_buf)
 
         if self.max_batch > 1:
             B, nhh = self.max_batch, self.nh_l * hd
@@ -522,6 +538,10 @@ class GPUModel:
             self.bt_cnt = torch.zeros(B, **i32)
             self.bt_sel = torch.zeros(B, ho.SAMPLE_SEL_WORDS, **i64)
             self.bt_samp = torch.zeros(B, ho.SAMP_WORDS, **i32)
+            # ... and the lockstep rows'
+            self._bv = RowState(self.bt_samp, self.bt_gmax, self.bt_pick,
+                                self.bt_cnt, self.bt_sel, self.bt_next,
+                                self.bt_ring, self.bt_nout, self.bt_lens)
             self.bt_scratch = torch.zeros(
                 B * self.nh_l * self.attn_split * (hd + 2),
                 dtype=torch.float32, device=dev)
@@ -770,18 +790,9 @@ class GPUModel:
         """Final norm + lm_head on the last row -> self.b_logits (f32, V);
         the norm rides in the GEMV staging pass (no separate launch)."""
         hrow = self.b_h[M - 1] if M > 1 else self.b_h[0]
-        kw = dict(stage=ho.STAGE_NORM, g=self.g_final,
-                  eps=self.config.rms_norm_eps, softcap=self.final_softcap)
-        if self.wq4:
-            ho.gemv_fp4(self.lm_head_q4, self.lm_head_e4, hrow,
-                        self.b_logits_l, **kw)
-        elif self.fp8:
-            ho.gemv_fp8(self.lm_head_q, self.lm_head_s, hrow,
-                        self.b_logits_l, **kw)
-        else:
-            ho.gemv(self.lm_head, hrow, self.b_logits_l, **kw)
-        if self.tp_branch:
-            tpu.all_gather_into(self.b_logits, self.b_logits_l)
+        self._lm_head_gemv(hrow, stage=ho.STAGE_NORM, g=self.g_final,
+                           eps=self.config.rms_norm_eps,
+                           softcap=self.final_softcap)
 
     def forward_full(self, ids: np.ndarray,
                      return_hidden_states: bool = False):
@@ -1041,19 +1052,6 @@ class GPUModel:
         if self._lp_rows.pop(b, None) is not None:
             ho.logprob_set_cfg(self.lp_cfg, b, -1)
 
-    def _lp_scan(self, logits, sl: slice, proc: bool):
-        """Logprob scan of the RAW rows ``logits`` (state rows ``sl``);
-        steps that adjust the logits next also snapshot them."""
-        raw = self.lp_raw[sl] if proc else None
-        ho.logprob_scan(logits, self.lp_cfg[sl], self.lp_part[sl],
-                        self.lp_stage[sl], raw=raw, batch=sl.stop - sl.start)
-
-    def _lp_commit(self, logits, sl: slice, proc: bool, next_token, nout):
-        raw = self.lp_raw[sl] if proc else None
-        ho.logprob_commit(logits, self.lp_cfg[sl], self.lp_stage[sl],
-                          next_token, nout, self.lp_val[sl], self.lp_idx[sl],
-                          raw=raw, batch=sl.stop - sl.start)
-
     def logprob_records(self, n: int, row: int = 0):
         """Records of the last ``n`` tokens committed on ``row``:
         ``(chosen_lp [n] f32, top_ids [n, N] i32, top_lp [n, N] f32)``
@@ -1111,43 +1109,61 @@ class GPUModel:
                              f"prefill_row(row_sampler=...)")
         return frozenset(self._samp_modes[b] for b in range(B))
 
-    @staticmethod
-    def _rows_key(rows) -> tuple:
-        """What of a mode set shapes the launch sequence: (any sampled
-        row, any top-k / top-p row).  No parameter VALUE is part of it."""
-        return (bool(rows - {ho.SAMP_GREEDY}),
-                bool(rows & {ho.SAMP_TOP_K, ho.SAMP_TOP_P}))
+    def _stage_setup(self, n: int, proc: bool, logprobs: bool,
+                     lp_batch: bool):
+        """State of the stages an ``n``-token decode call switches on:
+        processor rows, logprob rows (with the raw snapshot when the
+        logits are adjusted too); ``lp_batch``: the records follow
+        bt_nout (else nout)."""
+        if proc:
+            self._proc_alloc()
+        if logprobs:
+            if n > ho.LP_RING:
+                raise ValueError(f"logprobs: at most {ho.LP_RING} tokens "
+                                 f"per call, got {n}")
+            self._lp_alloc(raw=proc)
+            self._lp_batch = lp_batch
 
-    def _sample_step(self, greedy, min_p, temperature, top_k, top_p, rows):
-        """Sampler of the single-sequence decode step (``rows``: the mode
-        set of a ``row_sampler`` run, else the legacy arguments)."""
-        if rows is None:
-            ho.sample(self.b_logits, min_p, greedy, self.seed, self.rng_ctr,
-                      self.s_gmax, self.s_pick, self.next_token,
-                      self.out_ring, self.nout, self.len_buf, bump_len=True,
-                      temperature=temperature, cnt=self.s_cnt,
-                      top_k=top_k, top_p=top_p, sel=self.s_sel)
+    def _sample_tail(self, logits, v: RowState, B: int, spec: SampleSpec,
+                     first: bool = False, before_adjust=None):
+        """The end of every decode step, over ``B`` rows of ``logits``
+        and their state ``v``: logprob scan of the RAW rows (with a
+        snapshot when they are adjusted next), logit adjust, sampler,
+        logprob commit.  ``first``: the token after a prefill — nothing
+        generated yet, so the adjust stage counts no input and the
+        sampler leaves the length alone.  ``before_adjust`` runs between
+        scan and adjust (``prefill_row`` writes the row's processor
+        state there)."""
+        sl = v.sl or slice(0, B)
+        if spec.logprobs:
+            raw = self.lp_raw[sl] if spec.proc else None
+            ho.logprob_scan(logits, self.lp_cfg[sl], self.lp_part[sl],
+                            self.lp_stage[sl], raw=raw, batch=B)
+        if before_adjust is not None:
+            before_adjust()
+        if spec.proc:
+            # counts next_token (committed by the previous sample) into
+            # the history, then penalties + bias in place (the whole
+            # state goes with the tables from row 0, a narrowed one with
+            # its own rows)
+            pst = (self.p_stat, self.p_proc, self.p_bias)
+            if v.sl is not None:
+                pst = [t[v.sl] for t in pst]
+            ho.logit_adjust(logits, *pst, v.next_token, not first, batch=B)
+        if spec.rows is None:
+            ho.sample(logits, spec.min_p, spec.greedy, self.seed,
+                      self.rng_ctr, v.gmax, v.pick, v.next_token, v.ring,
+                      v.nout, v.lens, bump_len=not first,
+                      temperature=spec.temperature, cnt=v.cnt, batch=B,
+                      top_k=spec.top_k, top_p=spec.top_p, sel=v.sel)
         else:
-            ho.sample_rows(self.b_logits, self.s_samp, self.s_gmax,
-                           self.s_pick, self.s_cnt, self.next_token,
-                           self.out_ring, self.nout, self.len_buf,
-                           self.s_sel, 1, True, rows)
-
-    def _sample_batch_step(self, B, greedy, min_p, temperature, top_k,
-                           top_p, rows):
-        """Sampler of a lockstep decode step over bt_logits[:B]."""
-        if rows is None:
-            ho.sample(self.bt_logits[:B], min_p, greedy, self.seed,
-                      self.rng_ctr, self.bt_gmax, self.bt_pick, self.bt_next,
-                      self.bt_ring, self.bt_nout, self.bt_lens,
-                      bump_len=True, temperature=temperature,
-                      cnt=self.bt_cnt, batch=B,
-                      top_k=top_k, top_p=top_p, sel=self.bt_sel)
-        else:
-            ho.sample_rows(self.bt_logits[:B], self.bt_samp, self.bt_gmax,
-                           self.bt_pick, self.bt_cnt, self.bt_next,
-                           self.bt_ring, self.bt_nout, self.bt_lens,
-                           self.bt_sel, B, True, rows)
+            ho.sample_rows(logits, v.samp, v.gmax, v.pick, v.cnt,
+                           v.next_token, v.ring, v.nout, v.lens, v.sel, B,
+                           not first, spec.rows)
+        if spec.logprobs:
+            ho.logprob_commit(logits, self.lp_cfg[sl], self.lp_stage[sl],
+                              v.next_token, v.nout, self.lp_val[sl],
+                              self.lp_idx[sl], raw=raw, batch=B)
 
     def generate_tokens(self, prompt_ids, max_tokens: int,
                         greedy: bool = True, min_p: float = 0.1,
@@ -1292,10 +1308,30 @@ class GPUModel:
         else:
             ho.gemv(lw[name], x, y, **kw)
 
+    def _lm_head_gemv(self, x, **kw):
+        """lm_head over the staged row ``x`` -> b_logits (f32, V): the
+        engine's own ``lm_head*`` tensors through ``_dgemv``, then the
+        vocab all-gather under TP."""
+        self._dgemv(vars(self), "lm_head", x, self.b_logits_l, **kw)
+        if self.tp_branch:
+            tpu.all_gather_into(self.b_logits, self.b_logits_l)
+
     def _decode_step(self, greedy: bool, min_p: float,
                      temperature: float = 1.0, top_k: int = 0,
                      top_p: float = 1.0, proc: bool = False,
                      logprobs: bool = False, rows=None):
+        """One single-sequence decode step with the sampler request given
+        as plain arguments (see ``_step``)."""
+        self._step(SampleSpec(greedy, min_p, temperature, top_k, top_p,
+                              proc, logprobs, rows))
+
+    def _step(self, spec: SampleSpec):
+        """One single-sequence decode step: layer stack, then the
+        sampling tail on b_logits.  Graph-replayable."""
+        self._decode_layers()
+        self._sample_tail(self.b_logits, self._sv, 1, spec)
+
+    def _decode_layers(self):
         """Fused decode path: 4 kernels/layer (llama) or 5 (gemma) —
         RMSNorm lives inside the GEMV staging pass, RoPE + KV write
         inside the attention kernel.  bf16 weights: the gate+up GEMV
@@ -1421,43 +1457,14 @@ class GPUModel:
             # last layer's post-ffn sandwich norm + final norm, both
             # fused into the lm_head staging (NORM2: h' = h + norm(t2)*
             # g_postffn, then stage norm(h')*g_final)
-            kw = dict(stage=ho.STAGE_NORM2, x2=h,
-                      g=self.layers[-1]["g_postffn"], g2=self.g_final,
-                      res=hnext, eps=eps, softcap=self.final_softcap)
-            if self.wq4:
-                ho.gemv_fp4(self.lm_head_q4, self.lm_head_e4, t2,
-                            self.b_logits_l, **kw)
-            elif self.fp8:
-                ho.gemv_fp8(self.lm_head_q, self.lm_head_s, t2,
-                            self.b_logits_l, **kw)
-            else:
-                ho.gemv(self.lm_head, t2, self.b_logits_l, **kw)
+            self._lm_head_gemv(t2, stage=ho.STAGE_NORM2, x2=h,
+                               g=self.layers[-1]["g_postffn"],
+                               g2=self.g_final, res=hnext, eps=eps,
+                               softcap=self.final_softcap)
         else:
             # final norm fused into the lm_head staging pass
-            kw = dict(stage=ho.STAGE_NORM, g=self.g_final, eps=eps,
-                      softcap=self.final_softcap)
-            if self.wq4:
-                ho.gemv_fp4(self.lm_head_q4, self.lm_head_e4, h,
-                            self.b_logits_l, **kw)
-            elif self.fp8:
-                ho.gemv_fp8(self.lm_head_q, self.lm_head_s, h,
-                            self.b_logits_l, **kw)
-            else:
-                ho.gemv(self.lm_head, h, self.b_logits_l, **kw)
-        if self.tp_branch:
-            tpu.all_gather_into(self.b_logits, self.b_logits_l)
-        if logprobs:
-            # max / log-sum + top-N of the RAW row (ahead of any adjustment)
-            self._lp_scan(self.b_logits, slice(0, 1), proc)
-        if proc:
-            # counts next_token (committed by the previous sample) into
-            # the history, then penalties + bias in place
-            ho.logit_adjust(self.b_logits, self.p_stat, self.p_proc,
-                            self.p_bias, self.next_token, True)
-        self._sample_step(greedy, min_p, temperature, top_k, top_p, rows)
-        if logprobs:
-            self._lp_commit(self.b_logits, slice(0, 1), proc,
-                            self.next_token, self.nout)
+            self._lm_head_gemv(h, stage=ho.STAGE_NORM, g=self.g_final,
+                               eps=eps, softcap=self.final_softcap)
 
     # ------------------------------------------------------------------
     # lockstep batched decode (throughput mode; beyond-parity capability)
@@ -1466,29 +1473,38 @@ class GPUModel:
                            temperature: float = 1.0, top_k: int = 0,
                            top_p: float = 1.0, proc: bool = False,
                            logprobs: bool = False, rows=None):
-        """One decode step for B lockstep sequences.  fp8 weights with
-        B<=8 take the fused MULTI-X GEMV path (one weight stream feeds
-        B accumulators — near single-sequence step time); otherwise the
-        layer stack runs as M=B-row MFMA GEMMs.  Graph-replayable
-        (all state device-side)."""
-        cfg = self.config
+        """One lockstep decode step with the sampler request given as
+        plain arguments (see ``_batch_step``)."""
+        self._batch_step(B, SampleSpec(greedy, min_p, temperature, top_k,
+                                       top_p, proc, logprobs, rows))
+
+    def _batch_step(self, B: int, spec: SampleSpec):
+        """One decode step for B lockstep sequences: layer stack into
+        bt_logits[:B], then the sampling tail.  fp8 weights take a fused
+        stack (`_batch_layers_fused`) — the skinny fp8 MFMA GEMM up to
+        B=16, or with LLM_BATCH_MX_MAX the multi-x GEMV (one weight
+        stream feeds B accumulators); otherwise the layer stack runs as
+        M=B-row MFMA GEMMs.  Graph-replayable (all state device-side)."""
         # measured (profiles/decode_kernels_r02.md): the SKINNY fp8 MFMA
         # GEMM wins at every B (even B=2: 1.34 vs the multi-x GEMV's
         # 1.44 ms — the GEMV is VALU-ISSUE-bound, 64 irreducible
         # v_pk_fma per 16 weight bytes at B=8).  The multi-x path stays
         # available via LLM_BATCH_MX_MAX for comparison.
         import os as _os  # noqa: delayed so env changes apply per call
+        cfg = self.config
         mx_max = int(_os.environ.get("LLM_BATCH_MX_MAX", "0"))
         if (self.fp8 and B <= mx_max and not cfg.attention_bias
                 and not self.moe):
-            return self._decode_batch_step_mx(B, greedy, min_p, temperature,
-                                              top_k, top_p, proc, logprobs,
-                                              rows)
-        if self.fp8 and B <= 16 and not self.moe:
-            return self._decode_batch_step_skinny(B, greedy, min_p,
-                                                  temperature, top_k,
-                                                  top_p, proc, logprobs,
-                                                  rows)
+            self._batch_layers_fused(B, partial(self._proj_mx, B))
+        elif self.fp8 and B <= 16 and not self.moe:
+            self._batch_layers_fused(B, partial(self._proj_skinny, B))
+        else:
+            self._batch_layers_gemm(B)
+        self._sample_tail(self.bt_logits[:B], self._bv, B, spec)
+
+    def _batch_layers_gemm(self, B: int):
+        """Lockstep layer stack as M=B-row MFMA GEMMs (any dtype, MoE)."""
+        cfg = self.config
         ho.embed(self.embed, self.bt_next, self.b_h, B, cfg.embed_scale)
         self._layers_forward(B, batch_attn=True)
         ho.rmsnorm(self.b_h[:B], self.g_final, self.b_xn[:B],
@@ -1503,22 +1519,31 @@ class GPUModel:
                     accbuf=self.b_gemm_acc)
         if self.final_softcap:
             ho.softcap(self.bt_logits[:B], self.final_softcap)
-        if logprobs:
-            self._lp_scan(self.bt_logits[:B], slice(0, B), proc)
-        if proc:
-            self._adjust_rows(B)
-        self._sample_batch_step(B, greedy, min_p, temperature, top_k, top_p,
-                                rows)
-        if logprobs:
-            self._lp_commit(self.bt_logits[:B], slice(0, B), proc,
-                            self.bt_next, self.bt_nout)
 
-    def _decode_batch_step_mx(self, B: int, greedy: bool, min_p: float,
-                              temperature: float = 1.0, top_k: int = 0,
-                              top_p: float = 1.0, proc: bool = False,
-                              logprobs: bool = False, rows=None):
-        """Fused batched decode (fp8, B<=8): mirrors _decode_step's
-        4-5 kernels/layer with multi-x GEMVs over B rows."""
+    def _proj_mx(self, B, wq, ws, x, xstride, y, K, N, *, res=None,
+                 bias=None, softcap=0.0, **stage_kw):
+        """y[B, N] = W @ stage(x): ONE multi-x fp8 GEMV, the staging op
+        (norm / embed / GLU) inside it.  Strides in elements."""
+        assert bias is None, "bias models take the skinny path"
+        ho.gemv_fp8_mx(wq, ws, x, y, B, xstride, N, res=res,
+                       rstride=N if res is not None else 0,
+                       softcap=softcap, **stage_kw)
+
+    def _proj_skinny(self, B, wq, ws, x, xstride, y, K, N, *, res=None,
+                     bias=None, softcap=0.0, **stage_kw):
+        """The same projection as a (stage + e4m3 quant of the K-long
+        rows, skinny fp8 MFMA GEMM) pair: B up to 16, W streamed once."""
+        ho.stage_quant_mx(x, xstride, self.b_xq, self.b_sx, B, K, **stage_kw)
+        ho.gemm_fp8_skinny(self.b_xq, self.b_sx, wq, ws, y, B, N, res=res,
+                           rstride=N if res is not None else 0, bias=bias,
+                           softcap=softcap, accbuf=self.b_gemm_acc)
+
+    def _batch_layers_fused(self, B: int, proj):
+        """Fused lockstep layer stack (fp8): mirrors `_decode_layers`'
+        4-5 projections per layer over B rows, each one ``proj(wq, ws, x,
+        xstride, y, K, N, res=, bias=, softcap=, **stage_kw)`` with the
+        norm / embed gather / GLU as its staging op (`_proj_mx` or
+        `_proj_skinny`)."""
         cfg = self.config
         eps = cfg.rms_norm_eps
         H, I = self.H, self.inter_l
@@ -1527,26 +1552,31 @@ class GPUModel:
         t1, t2, gu = self.bt_t1, self.bt_t2, self.bt_gu
         qkvw = (self.nh_l + 2 * self.kvh_l) * self.hd
         nhh = self.nh_l * self.hd
+        glu = dict(stage=ho.STAGE_GLU, x2=gu[:, I:], x2stride=2 * I,
+                   act=self.act)
+
+        def norm2(g, g2):
+            # h' = h + norm(x)*g persisted to the other h buffer, stage
+            # norm(h')*g2: both gemma sandwich norms in one staging pass
+            return dict(stage=ho.STAGE_NORM2, x2=h, x2stride=H, g=g, g2=g2,
+                        hout=hb, hstride=H, eps=eps)
         prev = None
         for i, lw in enumerate(self.layers):
             window = cfg.sliding_window if cfg.is_sliding(i) else 0
+            x, xstride = h, H
             if self.gemma and prev is not None:
-                ho.gemv_fp8_mx(lw["wqkv_q"], lw["wqkv_s"], t2, self.bt_qkv,
-                               B, H, qkvw, stage=ho.STAGE_NORM2, x2=h,
-                               x2stride=H, g=prev["g_postffn"],
-                               g2=lw["g_in"], hout=hb, hstride=H, eps=eps)
+                x, st = t2, norm2(prev["g_postffn"], lw["g_in"])
                 h, hb = hb, h
             elif i == 0:
-                ho.gemv_fp8_mx(lw["wqkv_q"], lw["wqkv_s"], self.embed,
-                               self.bt_qkv, B, 0, qkvw,
-                               stage=ho.STAGE_NORM_EMBED,
-                               x2=self.bt_next, g=lw["g_in"], hout=h,
-                               hstride=H, eps=eps,
-                               escale=cfg.embed_scale)
+                # embed gather fused into the QKV staging pass
+                x, xstride = self.embed, 0
+                st = dict(stage=ho.STAGE_NORM_EMBED, x2=self.bt_next,
+                          g=lw["g_in"], hout=h, hstride=H, eps=eps,
+                          escale=cfg.embed_scale)
             else:
-                ho.gemv_fp8_mx(lw["wqkv_q"], lw["wqkv_s"], h, self.bt_qkv,
-                               B, H, qkvw, stage=ho.STAGE_NORM,
-                               g=lw["g_in"], eps=eps)
+                st = dict(stage=ho.STAGE_NORM, g=lw["g_in"], eps=eps)
+            proj(lw["wqkv_q"], lw["wqkv_s"], x, xstride, self.bt_qkv, H,
+                 qkvw, bias=lw.get("bqkv"), **st)
             prev = lw
             ho.attn_dec(self.bt_qkv, self.k_cache[i], self.v_cache[i],
                         self.b_att[0], self.bt_lens, self.cos_t, self.sin_t,
@@ -1556,152 +1586,25 @@ class GPUModel:
                         split=self.attn_split, kS=self.k_scale[i],
                         vS=self.v_scale[i], batch=B)
             if self.gemma:
-                ho.gemv_fp8_mx(lw["wo_q"], lw["wo_s"], self.b_att, t1, B,
-                               nhh, H)
-                ho.gemv_fp8_mx(lw["wgu_q"], lw["wgu_s"], t1, gu, B, H,
-                               2 * I, stage=ho.STAGE_NORM2, x2=h,
-                               x2stride=H, g=lw["g_post"],
-                               g2=lw["g_preffn"], hout=hb, hstride=H,
-                               eps=eps)
+                proj(lw["wo_q"], lw["wo_s"], self.b_att, nhh, t1, nhh, H)
+                proj(lw["wgu_q"], lw["wgu_s"], t1, H, gu, H, 2 * I,
+                     **norm2(lw["g_post"], lw["g_preffn"]))
                 h, hb = hb, h
-                ho.gemv_fp8_mx(lw["wdown_q"], lw["wdown_s"], gu, t2, B,
-                               2 * I, H, stage=ho.STAGE_GLU,
-                               x2=gu[:, I:], x2stride=2 * I, act=self.act)
+                proj(lw["wdown_q"], lw["wdown_s"], gu, 2 * I, t2, I, H,
+                     **glu)
             else:
-                ho.gemv_fp8_mx(lw["wo_q"], lw["wo_s"], self.b_att, h, B,
-                               nhh, H, res=h, rstride=H)
-                ho.gemv_fp8_mx(lw["wgu_q"], lw["wgu_s"], h, gu, B, H,
-                               2 * I, stage=ho.STAGE_NORM, g=lw["g_post"],
-                               eps=eps)
-                ho.gemv_fp8_mx(lw["wdown_q"], lw["wdown_s"], gu, h, B,
-                               2 * I, H, stage=ho.STAGE_GLU, x2=gu[:, I:],
-                               x2stride=2 * I, act=self.act, res=h,
-                               rstride=H)
+                proj(lw["wo_q"], lw["wo_s"], self.b_att, nhh, h, nhh, H,
+                     res=h)
+                proj(lw["wgu_q"], lw["wgu_s"], h, H, gu, H, 2 * I,
+                     stage=ho.STAGE_NORM, g=lw["g_post"], eps=eps)
+                proj(lw["wdown_q"], lw["wdown_s"], gu, 2 * I, h, I, H,
+                     res=h, **glu)
         if self.gemma:
-            ho.gemv_fp8_mx(self.lm_head_q, self.lm_head_s, t2,
-                           self.bt_logits, B, H, self.vocab_l,
-                           stage=ho.STAGE_NORM2, x2=h, x2stride=H,
-                           g=self.layers[-1]["g_postffn"], g2=self.g_final,
-                           hout=hb, hstride=H, eps=eps,
-                           softcap=self.final_softcap)
+            x, st = t2, norm2(self.layers[-1]["g_postffn"], self.g_final)
         else:
-            ho.gemv_fp8_mx(self.lm_head_q, self.lm_head_s, h,
-                           self.bt_logits, B, H, self.vocab_l,
-                           stage=ho.STAGE_NORM, g=self.g_final, eps=eps,
-                           softcap=self.final_softcap)
-        if logprobs:
-            self._lp_scan(self.bt_logits[:B], slice(0, B), proc)
-        if proc:
-            self._adjust_rows(B)
-        self._sample_batch_step(B, greedy, min_p, temperature, top_k, top_p,
-                                rows)
-        if logprobs:
-            self._lp_commit(self.bt_logits[:B], slice(0, B), proc,
-                            self.bt_next, self.bt_nout)
-
-    def _decode_batch_step_skinny(self, B: int, greedy: bool,
-                                  min_p: float, temperature: float = 1.0,
-                                  top_k: int = 0, top_p: float = 1.0,
-                                  proc: bool = False,
-                                  logprobs: bool = False, rows=None):
-        """Batched decode via (stage+quant, skinny fp8 MFMA GEMM) pairs:
-        B = 3..16 lockstep rows, W streamed once per projection."""
-        cfg = self.config
-        eps = cfg.rms_norm_eps
-        H, I = self.H, self.inter_l
-        h = self.b_h
-        hb = self.bt_hb
-        t1, t2, gu = self.bt_t1, self.bt_t2, self.bt_gu
-        qkvw = (self.nh_l + 2 * self.kvh_l) * self.hd
-        nhh = self.nh_l * self.hd
-        xq, sx = self.b_xq, self.b_sx
-        prev = None
-        for i, lw in enumerate(self.layers):
-            window = cfg.sliding_window if cfg.is_sliding(i) else 0
-            if self.gemma and prev is not None:
-                ho.stage_quant_mx(t2, H, xq, sx, B, H, stage=ho.STAGE_NORM2,
-                                  x2=h, x2stride=H, g=prev["g_postffn"],
-                                  g2=lw["g_in"], hout=hb, hstride=H,
-                                  eps=eps)
-                h, hb = hb, h
-            elif i == 0:
-                ho.stage_quant_mx(self.embed, 0, xq, sx, B, H,
-                                  stage=ho.STAGE_NORM_EMBED,
-                                  x2=self.bt_next, g=lw["g_in"], hout=h,
-                                  hstride=H, eps=eps,
-                                  escale=cfg.embed_scale)
-            else:
-                ho.stage_quant_mx(h, H, xq, sx, B, H, stage=ho.STAGE_NORM,
-                                  g=lw["g_in"], eps=eps)
-            ho.gemm_fp8_skinny(xq, sx, lw["wqkv_q"], lw["wqkv_s"],
-                               self.bt_qkv, B, qkvw, bias=lw.get("bqkv"),
-                               accbuf=self.b_gemm_acc)
-            prev = lw
-            ho.attn_dec(self.bt_qkv, self.k_cache[i], self.v_cache[i],
-                        self.b_att[0], self.bt_lens, self.cos_t, self.sin_t,
-                        self.bt_scratch, self.bt_attn_cnt,
-                        self.nh_l, self.kvh_l, self.hd, self.scale,
-                        softcap=self.attn_softcap, window=window or 0,
-                        split=self.attn_split, kS=self.k_scale[i],
-                        vS=self.v_scale[i], batch=B)
-            ho.stage_quant_mx(self.b_att, nhh, xq, sx, B, nhh)
-            if self.gemma:
-                ho.gemm_fp8_skinny(xq, sx, lw["wo_q"], lw["wo_s"], t1, B, H,
-                                   accbuf=self.b_gemm_acc)
-                ho.stage_quant_mx(t1, H, xq, sx, B, H,
-                                  stage=ho.STAGE_NORM2, x2=h, x2stride=H,
-                                  g=lw["g_post"], g2=lw["g_preffn"],
-                                  hout=hb, hstride=H, eps=eps)
-                h, hb = hb, h
-                ho.gemm_fp8_skinny(xq, sx, lw["wgu_q"], lw["wgu_s"], gu, B,
-                                   2 * I, accbuf=self.b_gemm_acc)
-                ho.stage_quant_mx(gu, 2 * I, xq, sx, B, I,
-                                  stage=ho.STAGE_GLU, x2=gu[:, I:],
-                                  x2stride=2 * I, act=self.act)
-                ho.gemm_fp8_skinny(xq, sx, lw["wdown_q"], lw["wdown_s"],
-                                   t2, B, H, accbuf=self.b_gemm_acc)
-            else:
-                ho.gemm_fp8_skinny(xq, sx, lw["wo_q"], lw["wo_s"], h, B, H,
-                                   res=h, rstride=H,
-                                   accbuf=self.b_gemm_acc)
-                ho.stage_quant_mx(h, H, xq, sx, B, H, stage=ho.STAGE_NORM,
-                                  g=lw["g_post"], eps=eps)
-                ho.gemm_fp8_skinny(xq, sx, lw["wgu_q"], lw["wgu_s"], gu, B,
-                                   2 * I, accbuf=self.b_gemm_acc)
-                ho.stage_quant_mx(gu, 2 * I, xq, sx, B, I,
-                                  stage=ho.STAGE_GLU, x2=gu[:, I:],
-                                  x2stride=2 * I, act=self.act)
-                ho.gemm_fp8_skinny(xq, sx, lw["wdown_q"], lw["wdown_s"], h,
-                                   B, H, res=h, rstride=H,
-                                   accbuf=self.b_gemm_acc)
-        if self.gemma:
-            ho.stage_quant_mx(t2, H, xq, sx, B, H, stage=ho.STAGE_NORM2,
-                              x2=h, x2stride=H,
-                              g=self.layers[-1]["g_postffn"],
-                              g2=self.g_final, hout=hb, hstride=H, eps=eps)
-        else:
-            ho.stage_quant_mx(h, H, xq, sx, B, H, stage=ho.STAGE_NORM,
-                              g=self.g_final, eps=eps)
-        ho.gemm_fp8_skinny(xq, sx, self.lm_head_q, self.lm_head_s,
-                           self.bt_logits, B, self.vocab_l,
-                           softcap=self.final_softcap,
-                           accbuf=self.b_gemm_acc)
-        if logprobs:
-            self._lp_scan(self.bt_logits[:B], slice(0, B), proc)
-        if proc:
-            self._adjust_rows(B)
-        self._sample_batch_step(B, greedy, min_p, temperature, top_k, top_p,
-                                rows)
-        if logprobs:
-            self._lp_commit(self.bt_logits[:B], slice(0, B), proc,
-                            self.bt_next, self.bt_nout)
-
-    def _adjust_rows(self, B: int):
-        """Logit-adjust stage of a lockstep step: every row counts the
-        token its previous sample committed (bt_next), then applies its
-        own penalties / bias to its bt_logits row."""
-        ho.logit_adjust(self.bt_logits[:B], self.p_stat, self.p_proc,
-                        self.p_bias, self.bt_next, True, batch=B)
+            x, st = h, dict(stage=ho.STAGE_NORM, g=self.g_final, eps=eps)
+        proj(self.lm_head_q, self.lm_head_s, x, H, self.bt_logits, H,
+             self.vocab_l, softcap=self.final_softcap, **st)
 
     def prefill_batch(self, prompts) -> None:
         """Prefill B prompts (RAGGED lengths allowed) into per-sequence
@@ -1751,63 +1654,31 @@ class GPUModel:
         ``logprobs``: run the logprob stage for the rows switched on with
         ``setup_logprobs`` (read back with ``logprob_records``)."""
         B = self._batch_n
-        logprobs = bool(logprobs)
-        if logprobs:
-            if n_tokens > ho.LP_RING:
-                raise ValueError(f"logprobs: at most {ho.LP_RING} tokens "
-                                 f"per call, got {n_tokens}")
-            self._lp_alloc()
-            self._lp_batch = True
-        # (proc, logprobs) of the step functions; nothing when off
-        extra = (False, True) if logprobs else ()
+        spec = SampleSpec(greedy, min_p, temperature, top_k, top_p,
+                          logprobs=bool(logprobs))
+        self._stage_setup(n_tokens, False, spec.logprobs, lp_batch=True)
         if max(self._host_lens) + n_tokens > self.max_seq:
             raise ValueError("decode_batch would overflow the KV pool")
         self._host_lens = [p + n_tokens for p in self._host_lens]
         if first_from_logits:
             # first tokens from the prefill logits (fp32, batch rows)
-            if logprobs:
-                self._lp_scan(self.bt_logits32[:B], slice(0, B), False)
-            ho.sample(self.bt_logits32[:B], min_p, greedy, self.seed,
-                      self.rng_ctr, self.bt_gmax, self.bt_pick,
-                      self.bt_next, self.bt_ring, self.bt_nout,
-                      self.bt_lens, bump_len=False,
-                      temperature=temperature, cnt=self.bt_cnt, batch=B,
-                      top_k=top_k, top_p=top_p, sel=self.bt_sel)
-            if logprobs:
-                self._lp_commit(self.bt_logits32[:B], slice(0, B), False,
-                                self.bt_next, self.bt_nout)
+            self._sample_tail(self.bt_logits32[:B], self._bv, B, spec,
+                              first=True)
         n_steps = n_tokens - (1 if first_from_logits else 0)
-        key = ("batch", B, greedy, min_p, temperature, top_k, top_p)
-        if logprobs:
-            key += ("logprobs",)
+        key = spec.graph_key("decode_batch", B)
+        step = partial(self._batch_step, B, spec)
         if use_graph and n_steps > 0 and self._graph_mode != key \
-                and not getattr(self, "_graph_failed", False):
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                self._decode_batch_step(B, greedy, min_p, temperature,
-                                        top_k, top_p, *extra)
-            torch.cuda.current_stream().wait_stream(s)
-            torch.cuda.synchronize()
-            n_steps -= 1
-            try:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._decode_batch_step(B, greedy, min_p, temperature,
-                                            top_k, top_p, *extra)
-                self._graph = g
-                self._graph_mode = key
-            except Exception as e:
-                self._graph_failed = True
-                self._graph_error = e
-                use_graph = False
+                and not self._graph_failed:
+            g = self._warm_and_capture(step)
+            n_steps -= 1  # the warm-up was a real step
+            if g is not None:
+                self._graph, self._graph_mode = g, key
         if use_graph and self._graph_mode == key:
             for _ in range(n_steps):
                 self._graph.replay()
         else:
             for _ in range(n_steps):
-                self._decode_batch_step(B, greedy, min_p, temperature,
-                                        top_k, top_p, *extra)
+                step()
         torch.cuda.synchronize()
         n = int(self.bt_nout[0].item())
         out = self.bt_ring[:B, :n].cpu().numpy()
@@ -1865,46 +1736,28 @@ class GPUModel:
             self._samp_modes[b] = samp_mode
         else:
             self._samp_modes.pop(b, None)
-        if logprobs is not None:
-            if processors is not None:
-                self._lp_alloc(raw=True)
+        spec = SampleSpec(greedy, min_p, temperature, top_k, top_p,
+                          proc=processors is not None,
+                          logprobs=logprobs is not None,
+                          rows=(frozenset({samp_mode})
+                                if row_sampler is not None else None))
+        self._stage_setup(1, spec.proc, spec.logprobs, lp_batch=True)
+        if spec.logprobs:
             self.setup_logprobs(b, logprobs)
-            self._lp_batch = True
-            self._lp_scan(self.b_logits, rb, processors is not None)
         else:
             self._lp_clear(b)
-        if processors is not None:
-            self.setup_processors(b, ids, processors)
-            # nothing generated yet: adjust without counting
-            ho.logit_adjust(self.b_logits, self.p_stat[b:b + 1],
-                            self.p_proc[b:b + 1], self.p_bias[b:b + 1],
-                            self.bt_next[b:b + 1], False)
-        else:
+        if not spec.proc:
             self._proc_clear(b)
-        # first token for this row only (row-sliced sampler state)
-        if row_sampler is not None:
-            ho.sample_rows(self.b_logits, self.bt_samp[rb], self.bt_gmax[rb],
-                           self.bt_pick[rb], self.bt_cnt[rb],
-                           self.bt_next[rb], self.bt_ring[rb],
-                           self.bt_nout[rb], self.bt_lens[rb],
-                           self.bt_sel[rb], 1, False, {samp_mode})
-        else:
-            ho.sample(self.b_logits, min_p, greedy, self.seed, self.rng_ctr,
-                      self.bt_gmax[b:b + 1], self.bt_pick[b:b + 1],
-                      self.bt_next[b:b + 1], self.bt_ring[b:b + 1],
-                      self.bt_nout[b:b + 1], self.bt_lens[b:b + 1],
-                      bump_len=False, temperature=temperature,
-                      cnt=self.bt_cnt[b:b + 1], batch=1,
-                      top_k=top_k, top_p=top_p, sel=self.bt_sel[b:b + 1])
-        if logprobs is not None:
-            self._lp_commit(self.b_logits, rb, processors is not None,
-                            self.bt_next[rb], self.bt_nout[rb])
-        if not hasattr(self, "_host_lens") or self._host_lens is None:
-            self._host_lens = [0] * self.max_batch
+        # first token for this row only (row-sliced state); the row's
+        # processor state is written once the raw logits are scanned
+        self._sample_tail(
+            self.b_logits, self._bv.rows(rb), 1, spec, first=True,
+            before_adjust=(lambda: self.setup_processors(b, ids, processors))
+            if spec.proc else None)
         while len(self._host_lens) < self.max_batch:
             self._host_lens.append(0)
         self._host_lens[b] = P
-        self._batch_n = max(getattr(self, "_batch_n", 0), b + 1)
+        self._batch_n = max(self._batch_n, b + 1)
 
     def compact_row(self, dst: int, src: int):
         """Move sequence slot src -> dst (KV pools, scales, device row
@@ -1970,61 +1823,30 @@ class GPUModel:
         call — drain with ``logprob_records`` in between).
         Returns a list of B arrays: each row's n new token ids."""
         assert 1 <= B <= self.max_batch
-        processors = bool(processors)
-        if processors:
-            self._proc_alloc()
-        logprobs = bool(logprobs)
-        if logprobs:
-            if n > ho.LP_RING:
-                raise ValueError(f"logprobs: at most {ho.LP_RING} tokens "
-                                 f"per call, got {n}")
-            self._lp_alloc(raw=processors)
-            self._lp_batch = True
-        lpx = (True,) if logprobs else ()
+        processors, logprobs = bool(processors), bool(logprobs)
+        self._stage_setup(n, processors, logprobs, lp_batch=True)
         if max(self._host_lens[:B]) + n > self.max_seq:
             raise ValueError("decode_rows would overflow the KV pool")
         for b in range(B):
             self._host_lens[b] += n
-        key = ("batchc", B, greedy, min_p, temperature, top_k, top_p,
-               processors) + (("logprobs",) if logprobs else ())
-        if row_sampler:
-            rows = self._row_modes(B)
-            key = ("batchr", B) + self._rows_key(rows) + (processors,
-                                                          logprobs)
-            # the step bodies take the mode set after (proc, logprobs)
-            lpx = (logprobs, rows)
-        if not hasattr(self, "_bgraphs"):
-            self._bgraphs = {}
+        spec = SampleSpec(greedy, min_p, temperature, top_k, top_p,
+                          processors, logprobs,
+                          self._row_modes(B) if row_sampler else None)
+        key = spec.graph_key("decode_rows", B)
+        step = partial(self._batch_step, B, spec)
         g = self._bgraphs.get(key)
-        executed = 0
-        if (use_graph and g is None and n > 1
-                and not getattr(self, "_graph_failed", False)):
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                self._decode_batch_step(B, greedy, min_p, temperature,
-                                        top_k, top_p, processors, *lpx)
-            torch.cuda.current_stream().wait_stream(s)
-            torch.cuda.synchronize()
-            executed += 1  # the warm-up was a real step
-            try:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._decode_batch_step(B, greedy, min_p, temperature,
-                                            top_k, top_p, processors, *lpx)
+        remaining = n
+        if use_graph and g is None and n > 1 and not self._graph_failed:
+            g = self._warm_and_capture(step)
+            remaining -= 1  # the warm-up was a real step
+            if g is not None:
                 self._bgraphs[key] = g
-            except Exception as e:
-                self._graph_failed = True
-                self._graph_error = e
-                g = None
-        remaining = n - executed
         if g is not None and use_graph:
             for _ in range(remaining):
                 g.replay()
         else:
             for _ in range(remaining):
-                self._decode_batch_step(B, greedy, min_p, temperature,
-                                        top_k, top_p, processors, *lpx)
+                step()
         torch.cuda.synchronize()
         comm = tpu.xgmi_comm()
         if comm is not None:
@@ -2053,7 +1875,9 @@ class GPUModel:
         is preallocated and the position is a device scalar — SURVEY §7
         'graph must be shape-stable').  ``logprobs``: the step carries the
         logprob stage (scan ahead of the adjust stage, commit after the
-        sampler).
+        sampler).  ``rows``: the mode set of a ``row_sampler`` run.  The
+        arguments make a ``SampleSpec``; its ``graph_key`` is the mode the
+        single graph slot is cached under.
 
         NOTE: the warm-up executes ONE REAL decode step (advances the
         sequence by one token).  Returns ``(steps_taken, ok)``:
@@ -2063,46 +1887,49 @@ class GPUModel:
         capture failure ``ok`` is False, ``self._graph_failed`` is set
         (no further capture attempts) and the exception is kept in
         ``self._graph_error``."""
-        processors = bool(processors)
-        mode = (greedy, min_p, temperature, top_k, top_p, processors)
-        if rows is not None:
-            # per-row sampler: the stages the row's mode needs, no value
-            mode = ("rows",) + self._rows_key(rows) + (processors,)
-        lpx = (True,) if logprobs else ()
-        if logprobs:
-            # the logprob stage is part of the key; N is not (device data)
-            mode += ("logprobs",)
-            self._lp_alloc(raw=processors)
-        if rows is not None:
-            lpx = (bool(logprobs), rows)
+        spec = SampleSpec(greedy, min_p, temperature, top_k, top_p,
+                          bool(processors), bool(logprobs), rows)
+        # the stages are part of the key; the logprob top-N and, with
+        # rows, the sampler values are not (device data)
+        mode = spec.graph_key("decode")
+        if spec.logprobs:
+            self._lp_alloc(raw=spec.proc)
         if self._graph_mode == mode:
             return 0, True
-        if getattr(self, "_graph_failed", False):
+        if self._graph_failed:
             return 0, False
-        # warm-up (a real step) on a side stream, then capture
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            self._decode_step(greedy, min_p, temperature, top_k, top_p,
-                              processors, *lpx)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        try:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._decode_step(greedy, min_p, temperature, top_k, top_p,
-                                  processors, *lpx)
-        except Exception as e:
-            # the warm-up step above DID run (token committed to
-            # out_ring, len_buf advanced) — report it so decode() does
-            # not double-count (ADVICE r1 medium)
-            self._graph_failed = True
-            self._graph_error = e
+        g = self._warm_and_capture(partial(self._step, spec))
+        if g is None:
+            # the warm-up step DID run (token committed to out_ring,
+            # len_buf advanced) — report it so decode() does not
+            # double-count (ADVICE r1 medium)
             torch.cuda.synchronize()
             return 1, False
         self._graph = g
         self._graph_mode = mode
         return 1, True
+
+    def _warm_and_capture(self, step):
+        """``step()`` once on a side stream — a REAL decode step, the
+        caller accounts for it — then captured into a hipGraph.  Returns
+        the graph, or None when capture failed: ``_graph_failed`` is then
+        set (no further capture attempts) and the exception kept in
+        ``_graph_error``."""
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            step()
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        try:
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                step()
+        except Exception as e:
+            self._graph_failed = True
+            self._graph_error = e
+            return None
+        return g
 
     def prefill(self, ids: np.ndarray, cache: Optional[DeviceCacheHandle] = None):
         cache = cache or self.make_cache(self.max_seq)
@@ -2126,55 +1953,25 @@ class GPUModel:
         ``row_sampler``: sample with the settings ``generate_tokens`` wrote
         to the single-sequence sampler table (greedy / min_p / temperature
         / top_k / top_p are then unused)."""
-        processors = bool(processors)
-        if processors:
-            self._proc_alloc()
-        logprobs = bool(logprobs)
-        if logprobs:
-            if n_tokens > ho.LP_RING:
-                raise ValueError(f"logprobs: at most {ho.LP_RING} tokens "
-                                 f"per call, got {n_tokens}")
-            self._lp_alloc(raw=processors)
-            self._lp_batch = False
-        lpx = (True,) if logprobs else ()
-        rows = self._s_rows if row_sampler else None
-        if rows is not None:
-            # the step takes the mode set after (proc, logprobs)
-            lpx = (logprobs, rows)
-        if getattr(self, "_host_len", 0) + n_tokens > self.max_seq:
+        spec = SampleSpec(greedy, min_p, temperature, top_k, top_p,
+                          bool(processors), bool(logprobs),
+                          self._s_rows if row_sampler else None)
+        self._stage_setup(n_tokens, spec.proc, spec.logprobs, lp_batch=False)
+        if self._host_len + n_tokens > self.max_seq:
             raise ValueError(
                 f"decode would overflow the KV pool: len {self._host_len} "
                 f"+ {n_tokens} > max_seq {self.max_seq}")
         self._host_len += n_tokens
         if first_from_logits:
             # sample token 0 from the prefill logits
-            if logprobs:
-                self._lp_scan(self.b_logits, slice(0, 1), processors)
-            if processors:
-                ho.logit_adjust(self.b_logits, self.p_stat, self.p_proc,
-                                self.p_bias, self.next_token, False)
-            if rows is not None:
-                ho.sample_rows(self.b_logits, self.s_samp, self.s_gmax,
-                               self.s_pick, self.s_cnt, self.next_token,
-                               self.out_ring, self.nout, self.len_buf,
-                               self.s_sel, 1, False, rows)
-            else:
-                ho.sample(self.b_logits, min_p, greedy, self.seed,
-                          self.rng_ctr, self.s_gmax, self.s_pick,
-                          self.next_token, self.out_ring, self.nout,
-                          self.len_buf, bump_len=False,
-                          temperature=temperature, cnt=self.s_cnt,
-                          top_k=top_k, top_p=top_p, sel=self.s_sel)
-            if logprobs:
-                self._lp_commit(self.b_logits, slice(0, 1), processors,
-                                self.next_token, self.nout)
+            self._sample_tail(self.b_logits, self._sv, 1, spec, first=True)
         n_steps = n_tokens - (1 if first_from_logits else 0)
         if use_graph and n_steps > 0:
             # capture_decode_graph reports the warm-up step it executed
             # even when capture fails, so n_steps stays exact either way
-            taken, ok = self.capture_decode_graph(greedy, min_p, temperature,
-                                                  top_k, top_p, processors,
-                                                  *lpx)
+            taken, ok = self.capture_decode_graph(
+                greedy, min_p, temperature, top_k, top_p, spec.proc,
+                spec.logprobs, spec.rows)
             n_steps -= taken
             if not ok:
                 use_graph = False
@@ -2183,8 +1980,7 @@ class GPUModel:
                 self._graph.replay()
         else:
             for _ in range(n_steps):
-                self._decode_step(greedy, min_p, temperature, top_k, top_p,
-                                  processors, *lpx)
+                self._step(spec)
         torch.cuda.synchronize()
         comm = tpu.xgmi_comm()
         if comm is not None:
