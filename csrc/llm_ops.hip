@@ -3758,6 +3758,228 @@ extern "C" hipError_t launch_logprob_commit(const void* logits, int V,
 }
 
 // ====================================================================
+// Prompt logprobs: k_logprob_rows scores M teacher-forced rows at once —
+// the opposite shape of the decode stage above (hundreds to thousands of
+// rows, one number each and optionally a top-N, no ring, no sampler).
+// One 256-thread block per row, grid = M: no global atomics, no ticket,
+// no fences, no scratch to re-arm.
+//   logits  [M, V]  bf16 / fp32, contiguous rows
+//   targets [M]     i32   token whose logprob goes to val[r, 0]; < 0 = none
+//                         (0.0f is written; the host never reports it)
+//   val [M, 21] f32, idx [M, 20] i32: the ring's record layout; slots past
+//                         N are not touched
+// Element -> thread mapping is fixed by the element index alone: thread t
+// owns the 8 logits [s*2048 + 8t, +8) of every 2048-slice s.  A 16-byte
+// aligned row loads them as one 16 B vector (two for fp32), any other row
+// (bf16 with odd V: every second row) with scalar loads INTO THE SAME
+// SLOTS, so the arithmetic — and with it the output bits — depends on the
+// row's contents, V, the dtype and N only, never on the row's address.
+// Per thread an online (m, s): s = sum exp(l - m), rescaled when m grows;
+// at most ceil(V / 2048) groups of 8 pairwise-summed terms in sequence.
+// Block: M = max m_t, S = sum_t s_t * exp(m_t - M) through the fixed
+// wave-xor tree and ((w0 + w1) + w2) + w3.  exp is v_exp_f32 (__expf):
+// terms that matter have arguments near 0, where x * log2(e) rounds to
+// ~1e-7; log S is one accurate logf.
+// N = 0 is that single streaming pass and nothing else (no LDS list, no
+// barrier in the loop).  N > 0 keeps the row's best words in LDS behind a
+// running N-th-largest threshold tau: a slice appends only words > tau to
+// a 4096-word candidate list (tau = 0 before the first merge, so slice 0
+// appends everything); when fewer than 2048 free slots remain the list is
+// reduced to its top N (lp_wave_topn over 16 words per thread, then
+// lp_merge_waves) and tau becomes the N-th.  On unsorted data that is two
+// reductions per row — after slice 0 and at the end — instead of one per
+// slice; an ascending row degrades to one per slice and stays correct.
+// Appends land in arrival order, but packed words are unique, so the top
+// N of the list does not depend on that order.
+// ====================================================================
+#define LPR_CAP 4096        // candidate words in LDS (N > 0)
+#define LPR_EPT 16          // = LPR_CAP / 256
+
+template <bool BF>
+DEVINL void lpr_load8(const void* row, int i0, int V, bool al,
+                      float (&x)[8]) {
+  if (al && i0 + 8 <= V) {
+    if (BF) {
+      const u4v_ q = *(const u4v_*)((const u16*)row + i0);
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        x[2 * j] = __uint_as_float(q[j] << 16);
+        x[2 * j + 1] = __uint_as_float(q[j] & 0xffff0000u);
+      }
+    } else {
+      const f4v a = *(const f4v*)((const float*)row + i0);
+      const f4v b = *(const f4v*)((const float*)row + i0 + 4);
+#pragma unroll
+      for (int j = 0; j < 4; j++) { x[j] = a[j]; x[4 + j] = b[j]; }
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      const int i = i0 + j;
+      x[j] = i < V ? (BF ? b2f(((const u16*)row)[i])
+                         : ((const float*)row)[i])
+                   : -INFINITY;
+    }
+  }
+}
+
+DEVINL void lpr_accum(const float (&x)[8], float& m, float& s) {
+  const float g = fmaxf(fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3])),
+                        fmaxf(fmaxf(x[4], x[5]), fmaxf(x[6], x[7])));
+  if (g > m) { s *= __expf(m - g); m = g; }
+  if (m > -INFINITY)
+    s += ((__expf(x[0] - m) + __expf(x[1] - m)) +
+          (__expf(x[2] - m) + __expf(x[3] - m))) +
+         ((__expf(x[4] - m) + __expf(x[5] - m)) +
+          (__expf(x[6] - m) + __expf(x[7] - m)));
+}
+
+// candidate list -> its top N in cand[0, N) (0 = empty slot), *cnt = N;
+// returns the N-th (0 while the list is shorter).  Every thread calls it,
+// after a barrier that follows the last append.
+DEVINL uint64_t lpr_merge(unsigned long long* cand, unsigned long long* wl,
+                          int* cnt, int N) {
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int n = *cnt;
+  uint64_t c[LPR_EPT];
+#pragma unroll
+  for (int j = 0; j < LPR_EPT; j++) {
+    const int ci = j * 256 + t;
+    c[j] = ci < n ? cand[ci] : 0ull;
+  }
+  const uint64_t mine = lp_wave_topn<LPR_EPT>(c, N);
+  if (lane < N) wl[wv * N + lane] = mine;
+  __syncthreads();
+  if (wv == 0) {
+    const uint64_t top = lp_merge_waves(wl, N);
+    if (lane < N) cand[lane] = top;
+    if (lane == 0) *cnt = N;
+  }
+  __syncthreads();
+  return cand[N - 1];
+}
+
+template <bool BF, bool TOP>
+DEVINL void logprob_rows_body(const void* logits, int V,
+                              const int* targets, int N, float* val,
+                              int* idx) {
+  extern __shared__ unsigned long long lpr_cand[];  // LPR_CAP words if TOP
+  __shared__ float wm[4], wsum[4];
+  __shared__ unsigned long long wl[4 * LOGPROBS_MAX_TOP];
+  __shared__ int cnt;
+  const int r = blockIdx.x;
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const char* row = (const char*)logits + (size_t)r * V * (BF ? 2 : 4);
+  const bool al = ((uintptr_t)row & 15) == 0;
+  val += (size_t)r * (1 + LOGPROBS_MAX_TOP);
+  idx += (size_t)r * LOGPROBS_MAX_TOP;
+  float m = -INFINITY, s = 0.0f;
+  float x[8];
+
+  if (!TOP) {
+    // two slices per trip, both loads in flight before the arithmetic
+    int base = 0;
+    for (; base + LP_SLICE < V; base += 2 * LP_SLICE) {
+      float y[8];
+      lpr_load8<BF>(row, base + t * 8, V, al, x);
+      lpr_load8<BF>(row, base + LP_SLICE + t * 8, V, al, y);
+      lpr_accum(x, m, s);
+      lpr_accum(y, m, s);
+    }
+    if (base < V) {
+      lpr_load8<BF>(row, base + t * 8, V, al, x);
+      lpr_accum(x, m, s);
+    }
+  } else {
+    uint64_t tau = 0ull;
+    if (t == 0) cnt = 0;
+    __syncthreads();
+    for (int base = 0; base < V; base += LP_SLICE) {
+      // cnt only grows between merges and the thread that appended last
+      // reads it after its own append, so the OR sees the full count; the
+      // barrier also orders the appends ahead of the merge's reads
+      if (__syncthreads_or(cnt > LPR_CAP - LP_SLICE))
+        tau = lpr_merge(lpr_cand, wl, &cnt, N);
+      const int i0 = base + t * 8;
+      lpr_load8<BF>(row, i0, V, al, x);
+      lpr_accum(x, m, s);
+      uint64_t w[8];
+      int np = 0;
+#pragma unroll
+      for (int j = 0; j < 8; j++) {
+        w[j] = i0 + j < V ? pack_ki(fkey(x[j]), i0 + j) : 0ull;
+        np += w[j] > tau;
+      }
+      if (np) {
+        int pos = atomicAdd(&cnt, np);
+#pragma unroll
+        for (int j = 0; j < 8; j++)
+          if (w[j] > tau) lpr_cand[pos++] = w[j];
+      }
+    }
+    __syncthreads();
+    lpr_merge(lpr_cand, wl, &cnt, N);
+  }
+
+  const float wmax = lp_wave_max(m);
+  if (lane == 0) wm[wv] = wmax;
+  __syncthreads();
+  const float M = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
+  s = m > -INFINITY ? s * __expf(m - M) : 0.0f;
+  s = wave_reduce_sum(s);
+  if (lane == 0) wsum[wv] = s;
+  __syncthreads();
+  const float S = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+  const float logS = M > -INFINITY ? logf(S) : 0.0f;
+  if (t == 0) {
+    const int tok = targets[r];
+    float lp = 0.0f;
+    if (tok >= 0 && tok < V) {
+      const float l = BF ? b2f(((const u16*)row)[tok])
+                         : ((const float*)row)[tok];
+      lp = lp_sub(l, M, logS);
+    }
+    val[0] = lp;
+  }
+  if (TOP && t < N) {
+    // fewer than N logits in the row: id -1, logprob -inf
+    const uint64_t top = lpr_cand[t];
+    val[1 + t] = top ? lp_sub(fkey_inv((uint32_t)(top >> 32)), M, logS)
+                     : -INFINITY;
+    idx[t] = top ? unpack_idx(top) : -1;
+  }
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+k_logprob_rows(const void* __restrict__ logits, int V, int lbf16,
+               const int* __restrict__ targets, int N,
+               float* __restrict__ val, int* __restrict__ idx) {
+  if (N > 0) {
+    if (lbf16) logprob_rows_body<true, true>(logits, V, targets, N, val, idx);
+    else logprob_rows_body<false, true>(logits, V, targets, N, val, idx);
+  } else {
+    if (lbf16) logprob_rows_body<true, false>(logits, V, targets, 0, val, idx);
+    else logprob_rows_body<false, false>(logits, V, targets, 0, val, idx);
+  }
+}
+
+// rows: M >= 1 contiguous rows of V logits; top_n in 0..LOGPROBS_MAX_TOP
+extern "C" hipError_t launch_logprob_rows(const void* logits, int V,
+                                          int lbf16, int rows,
+                                          const void* targets, int top_n,
+                                          void* val, void* idx,
+                                          hipStream_t stream) {
+  if (V <= 0 || V > (1 << 30) || rows <= 0 || top_n < 0 ||
+      top_n > LOGPROBS_MAX_TOP)
+    return hipErrorInvalidValue;
+  const size_t lds = top_n > 0 ? LPR_CAP * sizeof(unsigned long long) : 0;
+  hipLaunchKernelGGL(k_logprob_rows, dim3(rows), dim3(256), lds, stream,
+                     logits, V, lbf16, (const int*)targets, top_n,
+                     (float*)val, (int*)idx);
+  return hipGetLastError();
+}
+
+// ====================================================================
 // Prefill GEMM: Y[M,N] = X[M,K] @ W[N,K]^T (+res), bf16 in/out, fp32 acc.
 // MFMA v_mfma_f32_16x16x32_bf16; 128x128 tile, BK=32, 4 waves (2x2),
 // each wave a 64x64 sub-tile (4x4 fragments).  LDS staged, padded rows.

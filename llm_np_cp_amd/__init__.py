@@ -13,6 +13,10 @@ Public API (reference parity + extensions; see docs/MIGRATING.md):
     load_model(name_or_dir, ..., lora=) -> (tokenizer, model, config)
     generate(prompt, tokenizer, model, ..., stop=, logprobs=)
         -> GenerateResult (streams)
+    score(prompt_or_ids, tokenizer, model, top_n=) -> ScoreResult —
+        teacher-forced per-token logprobs, NLL, perplexity
+    loglikelihood(context, continuation, tokenizer, model)
+        -> (sum_logprob, is_greedy)
     generate_speculative(prompt, tok, draft, target, ...) — greedy or
         stochastic speculative sampling
     ChatSession(tok, model) — multi-turn KV reuse
@@ -22,6 +26,7 @@ Public API (reference parity + extensions; see docs/MIGRATING.md):
 from .core.config import ModelConfig, preset_config, PRESETS
 from .runtime.generate import generate, load_model, ByteTokenizer, GenerateResult
 from .runtime.sampling import SamplingParams, sample_token
+from .runtime.score import ScoreResult, loglikelihood, score
 from .runtime.session import ChatSession
 from .runtime.speculative import generate_speculative
 
@@ -30,4 +35,5 @@ __all__ = [
     "ModelConfig", "preset_config", "PRESETS",
     "generate", "load_model", "ByteTokenizer", "GenerateResult",
     "SamplingParams", "sample_token", "generate_speculative", "ChatSession",
+    "score", "loglikelihood", "ScoreResult",
 ]

@@ -50,6 +50,11 @@ def main(argv=None):
     ap.add_argument("--no-cache", action="store_true",
                     help="stateless re-prefill each step (debug mode, "
                          "reference use_cache=False path)")
+    ap.add_argument("--score", metavar="TEXT", default=None,
+                    help="score TEXT instead of generating: per-token "
+                         "logprobs and the perplexity")
+    ap.add_argument("--top-logprobs", type=int, default=0,
+                    help="with --score: alternatives shown per token")
     args = ap.parse_args(argv)
 
     import llm_np_cp_amd as L
@@ -57,6 +62,18 @@ def main(argv=None):
     tok, model, cfg = L.load_model(args.model, backend=args.backend,
                                    dtype=args.dtype, max_seq=args.max_seq,
                                    kv_dtype=args.kv_dtype, lora=args.lora)
+    if args.score is not None:
+        res = L.score(args.score, tok, model, top_n=args.top_logprobs)
+        print(f"{res.token_ids[0]:>8}  {tok.decode(res.token_ids[:1])!r:<16}"
+              f"{'-':>12}")
+        for e in res.top[1:]:
+            alts = "  ".join(f"{t['token']!r}:{t['logprob']:.3f}"
+                             for t in e["top"])
+            print(f"{e['id']:>8}  {e['token']!r:<16}{e['logprob']:>12.4f}"
+                  + (f"  [{alts}]" if alts else ""))
+        print(f"tokens {len(res.token_ids)}  nll {res.nll:.4f}  "
+              f"perplexity {res.perplexity:.4f}")
+        return
     params = L.SamplingParams(strategy=args.strategy, min_p=args.min_p,
                               temperature=args.temperature, seed=args.seed)
     t0 = time.time()

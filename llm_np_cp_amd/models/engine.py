@@ -21,6 +21,7 @@ spec in SURVEY §2.4 rather than translated.
 
 from __future__ import annotations
 
+import gc
 from functools import partial
 from typing import Dict, Optional
 
@@ -127,6 +128,11 @@ class GPUModel:
         self._lp_rows = {}
         self._lp_batch = False  # records follow bt_nout (else nout)
         self.last_logprobs = None
+        # prompt scoring (prompt_logprobs): 0 under TP — the vocabulary is
+        # sharded, callers take the host path; scratch on first use
+        self.device_prompt_logprobs = \
+            ho.LOGPROBS_MAX_TOP if self.world == 1 else 0
+        self.pl_logits = self.pl_tgt = self.pl_val = self.pl_idx = None
         if self.world == 1:
             self.device_row_sampler = True
         # host mirror of the per-row sampler table: slot -> mode of every
@@ -923,6 +929,99 @@ class GPUModel:
         ho.i32_set(self.len_buf, pos0 + n)
         self._host_len = pos0 + n
         return out
+
+    # rows per lm_head GEMM + k_logprob_rows launch of prompt_logprobs
+    # (docs/KERNELS.md: bounds the logits scratch to PL_ROWS x V bf16)
+    PL_ROWS = 512
+
+    def _pl_alloc(self):
+        """Scratch of ``prompt_logprobs``, allocated by the first call and
+        kept: logits [min(PC, PL_ROWS), V] bf16, targets [max_seq] i32,
+        records val [max_seq, 21] f32 / idx [max_seq, 20] i32."""
+        assert self.world == 1, "device prompt logprobs are single-GPU"
+        if self.pl_logits is None:
+            dev, W = self.device, ho.LOGPROBS_MAX_TOP
+            self.pl_logits = torch.empty(
+                min(self.PC, self.PL_ROWS), self.config.vocab_size,
+                dtype=torch.bfloat16, device=dev)
+            self.pl_tgt = torch.full((self.max_seq,), -1, dtype=torch.int32,
+                                     device=dev)
+            self.pl_val = torch.zeros(self.max_seq, 1 + W,
+                                      dtype=torch.float32, device=dev)
+            self.pl_idx = torch.zeros(self.max_seq, W, dtype=torch.int32,
+                                      device=dev)
+
+    def prompt_logprobs(self, ids: np.ndarray, top_n: int = 0):
+        """Teacher-forced logprobs of a prompt, device-side: returns
+        ``(lp [n-1] f32, top_ids [n-1, N] i32, top_lp [n-1, N] f32)``
+        numpy arrays; entry t describes ``ids[t+1]`` given ``ids[:t+1]``
+        (``top_lp`` descending, ties by ascending id).  The pass is
+        ``forward_full``'s — reset, chunks of PC, final norm, lm_head GEMM
+        in the engine's weight dtype, final softcap — but the logits stay on
+        the device: ``k_logprob_rows`` reduces every row to one record and
+        only the records cross to the host, once, at the end.  Afterwards
+        the KV pool holds the prompt, the length is n and the last row's
+        logits are staged, so ``decode`` continues as after ``prefill``."""
+        ids = np.asarray(ids, dtype=np.int32).ravel()
+        n, N = len(ids), int(top_n)
+        if not self.device_prompt_logprobs:
+            raise ValueError("device prompt logprobs are single-GPU; use "
+                             "the host path (runtime.score) under TP")
+        if n < 2:
+            raise ValueError(f"scoring needs at least 2 tokens, got {n}")
+        if not 0 <= N <= self.device_prompt_logprobs:
+            raise ValueError(f"top_n must be within 0.."
+                             f"{self.device_prompt_logprobs}, got {N}")
+        if n > self.max_seq:
+            raise ValueError(f"sequence {n} exceeds max_seq {self.max_seq}")
+        V = self.config.vocab_size
+        if ids.min() < 0 or ids.max() >= V:
+            raise ValueError(f"token ids must be within [0, {V})")
+        self._pl_alloc()
+        self.reset()
+        # row t's target is ids[t+1] (across chunk boundaries too); the
+        # last row has none
+        tgt = np.empty(n, dtype=np.int32)
+        tgt[:-1] = ids[1:]
+        tgt[-1] = -1
+        self.pl_tgt[:n].copy_(torch.from_numpy(tgt))
+        sub = self.pl_logits.shape[0]
+        done = 0
+        while done < n:
+            M = min(n - done, self.PC)
+            self.ids_buf[:M].copy_(torch.from_numpy(ids[done:done + M]))
+            ho.i32_set(self.len_buf, done)
+            ho.embed(self.embed, self.ids_buf, self.b_h, M,
+                     self.config.embed_scale)
+            self._layers_forward(M)
+            ho.rmsnorm(self.b_h[:M], self.g_final, self.b_xn[:M],
+                       eps=self.config.rms_norm_eps)
+            for r0 in range(0, M, sub):
+                m = min(M - r0, sub)
+                x, y = self.b_xn[r0:r0 + m], self.pl_logits[:m]
+                if self.wq4:
+                    ho.gemm_fp4w(x, self.lm_head_q4, self.lm_head_e4, y,
+                                 accbuf=self.b_gemm_acc)
+                elif self.fp8:
+                    ho.quant_fp8(x, self.b_xq, self.b_sx)
+                    ho.gemm_fp8(self.b_xq, self.b_sx, self.lm_head_q,
+                                self.lm_head_s, y, m, self.H,
+                                accbuf=self.b_gemm_acc)
+                else:
+                    ho.gemm(x, self.lm_head, y, accbuf=self.b_gemm_acc)
+                if self.final_softcap:
+                    ho.softcap(y, self.final_softcap)
+                a = done + r0
+                ho.logprob_rows(y, self.pl_tgt[a:a + m], N,
+                                self.pl_val[a:a + m], self.pl_idx[a:a + m])
+            done += M
+        ho.i32_set(self.len_buf, n)
+        self._host_len = n
+        self._lm_head_last(M)
+        torch.cuda.synchronize()
+        val = self.pl_val[:n - 1].cpu().numpy()
+        idx = self.pl_idx[:n - 1].cpu().numpy()
+        return (val[:, 0].copy(), idx[:, :N].copy(), val[:, 1:1 + N].copy())
 
     def rewind(self, n: int):
         """Roll the sequence back to length n — O(1): the KV pool is
@@ -1921,6 +2020,15 @@ class GPUModel:
             step()
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
+        # No cyclic-garbage collection may land inside the capture: a dead
+        # cycle can hold another engine's tensors and captured graphs, and
+        # releasing those calls HIP APIs a capturing process must not make
+        # (the process aborts).  torch.cuda.graph() no longer collects on
+        # entry by default, so collect here and hold the collector off
+        # until the capture has ended.
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
         try:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
@@ -1929,6 +2037,9 @@ class GPUModel:
             self._graph_failed = True
             self._graph_error = e
             return None
+        finally:
+            if gc_was_on:
+                gc.enable()
         return g
 
     def prefill(self, ids: np.ndarray, cache: Optional[DeviceCacheHandle] = None):

@@ -86,6 +86,9 @@ _SIGS = {
                             ctypes.c_long] + [ctypes.c_void_p] * 3,
     "launch_logprob_commit": [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                               ctypes.c_int] + [ctypes.c_void_p] * 8,
+    "launch_logprob_rows": [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                            ctypes.c_int, ctypes.c_void_p, ctypes.c_int] +
+                           [ctypes.c_void_p] * 3,
     "launch_gemm_bf16": [ctypes.c_void_p] * 5 + [ctypes.c_int] * 3 +
                         [ctypes.c_void_p],
     "launch_softcap": [ctypes.c_void_p, ctypes.c_long, ctypes.c_float,
@@ -751,6 +754,51 @@ def logprob_commit(logits: torch.Tensor, lp_cfg: torch.Tensor,
         _ptr(logits), V, lbf16, batch, _ptr(lp_cfg), _ptr(stage), _ptr(raw),
         _ptr(next_token), _ptr(nout), _ptr(lp_val), _ptr(lp_idx),
         _stream()), "logprob_commit")
+
+
+def logprob_rows(logits: torch.Tensor, targets: torch.Tensor, top_n: int,
+                 val: torch.Tensor, idx: torch.Tensor):
+    """Teacher-forced scoring of M logits rows at once (fp32 or bf16
+    [M, V], contiguous): ``val[r, 0]`` (fp32 [M, 1 + LOGPROBS_MAX_TOP]) gets
+    the log-softmax of row r at ``targets[r]`` (int32 [M]; < 0 = no target,
+    0.0 is written), ``val[r, 1..top_n]`` / ``idx[r, :top_n]`` (int32
+    [M, LOGPROBS_MAX_TOP]) the row's top-N, descending, ties by ascending
+    id — the record layout of the decode ring, so ``logprob_entries`` reads
+    them unchanged.  Slots past ``top_n`` keep what they held; a row shorter
+    than N fills id -1 / logprob -inf.  ``top_n == 0`` is one streaming
+    pass.  A target >= V is a caller error: the targets are device data,
+    so callers range-check the ids on the host before uploading them (as
+    ``prompt_logprobs`` does); the kernel writes 0.0 for one rather than
+    read past the row."""
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"logits must be fp32 or bf16, got {logits.dtype}")
+    if logits.dim() != 2 or not logits.is_contiguous() \
+            or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise ValueError("logits must be contiguous [M >= 1, V >= 1]")
+    M, V = logits.shape
+    top_n = int(top_n)
+    if not 0 <= top_n <= LOGPROBS_MAX_TOP:
+        raise ValueError(f"top_n must be within 0..{LOGPROBS_MAX_TOP}, "
+                         f"got {top_n}")
+    if targets.dtype != torch.int32 or not targets.is_contiguous() \
+            or targets.dim() != 1 or targets.numel() != M:
+        raise ValueError("targets must be contiguous int32 [M]")
+    W = LOGPROBS_MAX_TOP
+    if val.dtype != torch.float32 or not val.is_contiguous() \
+            or val.dim() != 2 or val.shape[0] < M or val.shape[1] != 1 + W:
+        raise ValueError(f"val must be contiguous fp32 [>=M, {1 + W}]")
+    if idx.dtype != torch.int32 or not idx.is_contiguous() \
+            or idx.dim() != 2 or idx.shape[0] < M or idx.shape[1] != W:
+        raise ValueError(f"idx must be contiguous int32 [>=M, {W}]")
+    for name, t in (("targets", targets), ("val", val), ("idx", idx)):
+        if t.device != logits.device:
+            raise ValueError(f"{name} must live on the logits' device")
+    if not logits.is_cuda:
+        raise ValueError("logprob_rows runs on the GPU; got CPU tensors")
+    _check(lib().launch_logprob_rows(
+        _ptr(logits), V, 1 if logits.dtype == torch.bfloat16 else 0, M,
+        _ptr(targets), top_n, _ptr(val), _ptr(idx), _stream()),
+        "logprob_rows")
 
 
 def gemm(X: torch.Tensor, W: torch.Tensor, Y: torch.Tensor,

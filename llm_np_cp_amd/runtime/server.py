@@ -40,13 +40,14 @@ from typing import Optional
 try:  # pydantic model must live at module scope (ForwardRef resolution)
     from typing import Dict, Literal
 
-    from pydantic import BaseModel, Field
+    from pydantic import BaseModel, Field, model_validator
 
     _Strategy = Literal["min_p", "greedy", "top_k", "top_p", "temperature"]
 
     class CompletionRequest(BaseModel):
         prompt: str
-        max_tokens: int = Field(128, ge=1)
+        # 0 only as the scoring request echo + logprobs (validator below)
+        max_tokens: int = Field(128, ge=0)
         temperature: float = Field(1.0, gt=0)
         min_p: float = Field(0.1, ge=0, le=1)
         top_k: int = Field(50, ge=1)
@@ -65,7 +66,17 @@ try:  # pydantic model must live at module scope (ForwardRef resolution)
         presence_penalty: float = Field(0.0, ge=-2, le=2)
         frequency_penalty: float = Field(0.0, ge=-2, le=2)
         repetition_penalty: float = Field(1.0, gt=0)
-        echo: bool = False        # prepend the prompt to the text
+        # prepend the prompt to the text; with logprobs also the prompt
+        # tokens' logprobs ahead of the generated ones (first one null)
+        echo: bool = False
+
+        @model_validator(mode="after")
+        def _score_only(self):
+            if self.max_tokens == 0 and not (
+                    self.echo and self.logprobs is not None):
+                raise ValueError("max_tokens=0 is accepted only together "
+                                 "with echo=true and logprobs")
+            return self
 
     class ChatMessage(BaseModel):
         role: str
@@ -394,24 +405,52 @@ def build_app(model_name: str = "llama-3.2-1b", backend: str = "auto",
         return {
             "tokens": [e["token"] for e in entries],
             "token_logprobs": [e["logprob"] for e in entries],
-            "top_logprobs": [{t["token"]: t["logprob"] for t in e["top"]}
+            # a prompt's first token (echo) has no logprob: null / null
+            "top_logprobs": [None if e["top"] is None else
+                             {t["token"]: t["logprob"] for t in e["top"]}
                              for e in entries],
         }
+
+    def _prompt_entries(req) -> list:
+        """echo + logprobs: one entry per PROMPT token, the first with a
+        null logprob and null alternatives (OpenAI legacy semantics);
+        the rest scored teacher-forced (``score``: device path when the
+        engine advertises ``device_prompt_logprobs``)."""
+        ids = [int(i) for i in tok.encode(req.prompt)]
+        if not ids:
+            return []
+        first = {"id": ids[0], "token": tok.decode(ids[:1]),
+                 "logprob": None, "top": None}
+        if len(ids) < 2:
+            return [first]
+        res = L.score(ids, tok, model, top_n=int(req.logprobs))
+        return [first] + res.top[1:]
 
     def generate_one(req, on_token=None) -> dict:
         n = getattr(req, "n", 1) or 1
         t0 = time.time()
         pay = None
+        lp_n = getattr(req, "logprobs", None)
+        prompt_lp = (_prompt_entries(req)
+                     if getattr(req, "echo", False) and lp_n is not None
+                     else None)
         for idx in range(n):
             seed = (req.seed + idx) if (req.seed is not None and n > 1) \
                 else req.seed
             params = _sampling_params(req, seed)
-            out = L.generate(req.prompt, tok, model,
-                             max_tokens=req.max_tokens, params=params,
-                             stream=False, stop_on_eos=req.stop_on_eos,
-                             stop=getattr(req, "stop", None),
-                             logprobs=getattr(req, "logprobs", None),
-                             on_token=on_token if idx == 0 else None)
+            if req.max_tokens == 0:
+                # scoring request (echo + logprobs): the prompt alone
+                out = L.GenerateResult(text="", token_ids=[],
+                                       finish_reason="length", logprobs=[])
+            else:
+                out = L.generate(req.prompt, tok, model,
+                                 max_tokens=req.max_tokens, params=params,
+                                 stream=False, stop_on_eos=req.stop_on_eos,
+                                 stop=getattr(req, "stop", None),
+                                 logprobs=lp_n,
+                                 on_token=on_token if idx == 0 else None)
+            if prompt_lp is not None:
+                out.logprobs = prompt_lp + list(out.logprobs or [])
             text = (req.prompt + out.text
                     if getattr(req, "echo", False) else out.text)
             if pay is None:
