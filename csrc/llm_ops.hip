@@ -2799,9 +2799,11 @@ k_logit_max(const void* __restrict__ logits, int V, int lbf16,
 // temperatures / seeds share one launch sequence and one captured graph.
 #define SAMP_MODE 0  // 0 greedy, 1 min-p cut, 2 top-k, 3 top-p
 #define SAMP_INVT 1  // fp32 1 / temperature
-#define SAMP_MINP 2  // fp32 (mode 1; 0 = plain temperature sampling)
+#define SAMP_MINP 2  // fp32 (mode 1; 0 = plain temperature sampling;
+                     // modes 2 / 3: > 0 = a min-p cut on top of tau)
 #define SAMP_TOPK 3  // int, 1..V (mode 2)
-#define SAMP_TOPP 4  // fp32 (mode 3)
+#define SAMP_TOPP 4  // fp32 (mode 3; mode 2: < 1 = top-p WITHIN the top-k
+                     // survivors, the second select phase)
 #define SAMP_SEED 5  // 5, 6: the row's 64-bit seed (lo, hi)
 #define SAMP_CTR 7   // draws so far: zeroed by the host, advanced here
 #define SAMP_WORDS 8
@@ -2964,11 +2966,19 @@ k_sample_pick_sel(const void* __restrict__ logits, int V, int lbf16,
 // Per-row variant: mode, temperature, cut and seed come from samp[b], so
 // one launch serves rows of every strategy.  Keep-set per mode: 0 all
 // (plain argmax), 1 the min-p expression of k_sample_pick, 2 / 3
-// {fkey(l) >= tau} with tau from k_sample_select_rows.  The noise of
+// {fkey(l) >= tau} with tau from k_sample_select_rows, intersected with
+// the min-p expression where the row carries min_p > 0 (composed rows):
+// fkey is monotone, so l >= cut is fkey(l) >= fkey(cut) and the two cuts
+// fold into one key, tau = max(tau, fkey(cut)).  The noise of
 // element i is a function of (i, row seed, row counter) alone — neither
 // the slot b nor a shared counter enters — so a request's stream does not
-// depend on where it sits or on what its neighbours do.
-extern "C" __global__ void __launch_bounds__(256)
+// depend on where it sits or on what its neighbours do.  MINP: the
+// variant that reads the min-p word of selected rows, launched only when
+// the host says such a row is present, so groups of today's modes run the
+// code they ran (a kernel template, not a shared inline body: the
+// arguments keep their __restrict__ as kernel arguments).
+template <bool MINP>
+__global__ void __launch_bounds__(256)
 k_sample_pick_rows(const void* __restrict__ logits, int V, int lbf16,
                    long ring_stride, const uint32_t* __restrict__ samp,
                    unsigned long long* __restrict__ gmax,
@@ -2995,6 +3005,15 @@ k_sample_pick_rows(const void* __restrict__ logits, int V, int lbf16,
   else if (!greedy)
     thresh = fkey_inv((uint32_t)(*gmax >> 32)) +
              __logf(__uint_as_float(samp[SAMP_MINP])) / inv_temp;
+  if (MINP && selected) {
+    const float min_p = __uint_as_float(samp[SAMP_MINP]);
+    if (min_p > 0.0f) {
+      float cut = fkey_inv((uint32_t)(*gmax >> 32)) + __logf(min_p) / inv_temp;
+      if (cut == 0.0f) cut = -0.0f;  // -0 >= +0, but fkey(-0) < fkey(+0)
+      const uint32_t kc = fkey(cut);
+      if (kc > tau) tau = kc;
+    }
+  }
   // two per-draw keys: k0 mixes counter and seed lo, k1 adds seed hi
   const uint32_t k0 =
       hash32(hash32(samp[SAMP_CTR] ^ 0x9e3779b9u) ^ samp[SAMP_SEED]);
@@ -3031,6 +3050,19 @@ k_sample_pick_rows(const void* __restrict__ logits, int V, int lbf16,
 // the `last` pass the prefix is the threshold key tau (ties at tau are
 // kept).  A row that cannot reach its target (all-NaN / zero mass) falls
 // to bin 0 every pass: tau = 0 keeps everything, nothing loops.
+//
+// Composed top-k -> top-p (per-row sampler only) is two such descents.
+// Phase 1 is the count descent, unchanged; its last pass leaves tau_k in
+// SEL_TAU and in SEL_PREFIX.  Phase 2 (PHASE2) is the mass descent over
+// the WHOLE row, with the first-pass target ceil(top_p * M_k), M_k = the
+// fixed-point mass of {key >= tau_k}: the first pass sums M_k ON TOP of
+// the tau_k in SEL_PREFIX beside its histogram (a first pass reads no
+// prefix and only writes that word at its end, from the last arriver,
+// which subtracts tau_k again).  The same integer weights feed M_k and
+// the bins, so the suffix at tau_k holds exactly M_k >= target and the
+// descent ends at tau >= tau_k: no restriction to the survivors is
+// needed.
+template <bool PHASE2>
 DEVINL void sample_select_body(
     const void* __restrict__ logits, int V, int lbf16,
     int top_k, float top_p, float inv_temp, int shift,
@@ -3043,10 +3075,14 @@ DEVINL void sample_select_body(
   const float* lf = (const float*)logits + (size_t)b * V;
   const u16* lh = (const u16*)logits + (size_t)b * V;
   __shared__ unsigned long long sh[256];
+  __shared__ unsigned long long shm;  // PHASE2, first pass: block's M_k
   __shared__ int lastflag;
   sh[t] = 0ull;
+  if (PHASE2 && t == 0) shm = 0ull;
   __syncthreads();
   const bool first = shift == 24;
+  const uint32_t tau_k = (PHASE2 && first) ? (uint32_t)sel[SEL_TAU] : 0u;
+  unsigned long long mk = 0ull;
   const uint32_t prefix = first ? 0u : (uint32_t)sel[SEL_PREFIX];
   const uint32_t himask = first ? 0u : (0xffffffffu << (shift + 8));
   const float lmax = fkey_inv((uint32_t)(gmax[b] >> 32));
@@ -3061,7 +3097,9 @@ DEVINL void sample_select_body(
       w = (unsigned long long)(e * 1099511627776.0f);  // 2^40
     }
     if (w) atomicAdd(&sh[(key >> shift) & 255u], w);
+    if (PHASE2 && first && key >= tau_k) mk += w;
   }
+  if (PHASE2 && mk) atomicAdd(&shm, mk);
   __syncthreads();
   // wave 0 merges all 256 bins, so ONE wave's release fence (an L2
   // write-back) orders the whole block's contribution ahead of its
@@ -3075,6 +3113,9 @@ DEVINL void sample_select_body(
         __hip_atomic_fetch_add(&hist[t + 64 * j], hj, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
     }
+    if (PHASE2 && first && t == 0 && shm)
+      __hip_atomic_fetch_add(&sel[SEL_PREFIX], shm, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     if (t == 0) {
       unsigned long long tk = __hip_atomic_fetch_add(
@@ -3102,6 +3143,12 @@ DEVINL void sample_select_body(
   unsigned long long target;
   if (!first) {
     target = sel[SEL_TARGET];
+  } else if (PHASE2) {
+    const unsigned long long m_k =
+        __hip_atomic_load(&sel[SEL_PREFIX], __ATOMIC_RELAXED,
+                          __HIP_MEMORY_SCOPE_AGENT) - tau_k;
+    target = (unsigned long long)ceil((double)top_p * (double)m_k);
+    if (target == 0ull) target = 1ull;
   } else if (top_k > 0) {
     target = (unsigned long long)top_k;
   } else {
@@ -3125,8 +3172,8 @@ k_sample_select(const void* __restrict__ logits, int V, int lbf16,
                 int top_k, float top_p, float inv_temp, int shift,
                 int last, const unsigned long long* __restrict__ gmax,
                 unsigned long long* __restrict__ sel) {
-  sample_select_body(logits, V, lbf16, top_k, top_p, inv_temp, shift, last,
-                     gmax, sel);
+  sample_select_body<false>(logits, V, lbf16, top_k, top_p, inv_temp, shift,
+                            last, gmax, sel);
 }
 
 // Per-row variant: weight and first-pass target follow samp[b]'s mode
@@ -3142,10 +3189,28 @@ k_sample_select_rows(const void* __restrict__ logits, int V, int lbf16,
   samp += (size_t)blockIdx.y * SAMP_WORDS;
   const uint32_t mode = samp[SAMP_MODE];
   if (mode < 2u) return;
-  sample_select_body(logits, V, lbf16,
-                     mode == 2u ? (int)samp[SAMP_TOPK] : 0,
-                     __uint_as_float(samp[SAMP_TOPP]),
-                     __uint_as_float(samp[SAMP_INVT]), shift, last, gmax, sel);
+  sample_select_body<false>(logits, V, lbf16,
+                            mode == 2u ? (int)samp[SAMP_TOPK] : 0,
+                            __uint_as_float(samp[SAMP_TOPP]),
+                            __uint_as_float(samp[SAMP_INVT]), shift, last,
+                            gmax, sel);
+}
+
+// Second select phase of composed rows (mode 2 with top_p < 1): the mass
+// descent whose first-pass target is top_p of the top-k survivors' mass.
+// Launched only when the host says such a row is present; every other row
+// returns at once and keeps the tau phase 1 gave it.
+extern "C" __global__ void __launch_bounds__(256)
+k_sample_select_rows2(const void* __restrict__ logits, int V, int lbf16,
+                      const uint32_t* __restrict__ samp, int shift, int last,
+                      const unsigned long long* __restrict__ gmax,
+                      unsigned long long* __restrict__ sel) {
+  samp += (size_t)blockIdx.y * SAMP_WORDS;
+  const float top_p = __uint_as_float(samp[SAMP_TOPP]);
+  if (samp[SAMP_MODE] != 2u || !(top_p < 1.0f)) return;
+  sample_select_body<true>(logits, V, lbf16, 0, top_p,
+                           __uint_as_float(samp[SAMP_INVT]), shift, last,
+                           gmax, sel);
 }
 
 extern "C" hipError_t launch_sample(const void* logits, int V, int lbf16,
@@ -3229,14 +3294,18 @@ extern "C" hipError_t launch_sample_sel(
 //                                  launch_sample greedy launch
 //   no row in mode 2 / 3:          max + pick
 //   else:                          max + 4 (bf16: 2) select passes + pick
+//   chain & 1 (a mode-2 row with   the same, with 4 (bf16: 2) phase-2
+//   top_p < 1 is present):         passes between select and pick
+//   chain & 2 (a mode-2 / 3 row    the pick is the variant that reads the
+//   with min_p > 0 is present):    rows' min-p word
 // so a uniform group costs the launches it costs through the legacy
 // launchers.  A row whose mode the flags do not cover is a host error
 // (its keep-set would be the whole row).
 extern "C" hipError_t launch_sample_rows(
     const void* logits, int V, int lbf16, int batch, long ring_stride,
-    void* samp, int any_sampled, int any_select, void* gmax, void* pick,
-    void* cnt, void* next_token, void* out_ring, void* nout, void* len_ptr,
-    int bump_len, void* sel, hipStream_t stream) {
+    void* samp, int any_sampled, int any_select, int chain, void* gmax,
+    void* pick, void* cnt, void* next_token, void* out_ring, void* nout,
+    void* len_ptr, int bump_len, void* sel, hipStream_t stream) {
   int blocks = (V + 255) / 256;
   if (blocks > 512) blocks = 512;
   if (batch > 1) {
@@ -3268,8 +3337,18 @@ extern "C" hipError_t launch_sample_rows(
                          shift == last_shift ? 1 : 0,
                          (const unsigned long long*)gmax,
                          (unsigned long long*)sel);
+    if (chain & 1)
+      for (int shift = 24; shift >= last_shift; shift -= 8)
+        hipLaunchKernelGGL(k_sample_select_rows2, dim3(sblocks, batch),
+                           dim3(256), 0, stream, logits, V, lbf16,
+                           (const uint32_t*)samp, shift,
+                           shift == last_shift ? 1 : 0,
+                           (const unsigned long long*)gmax,
+                           (unsigned long long*)sel);
   }
-  hipLaunchKernelGGL(k_sample_pick_rows, dim3(blocks, batch), dim3(256), 0,
+  hipLaunchKernelGGL((chain & 2) ? k_sample_pick_rows<true>
+                                 : k_sample_pick_rows<false>,
+                     dim3(blocks, batch), dim3(256), 0,
                      stream, logits, V, lbf16, ring_stride,
                      (const uint32_t*)samp, (unsigned long long*)gmax,
                      (unsigned long long*)pick, (int*)cnt, (int*)next_token,

@@ -29,8 +29,12 @@ def main(argv=None):
     ap.add_argument("--kv-dtype", default="bf16", choices=["bf16", "fp8"])
     ap.add_argument("--strategy", default="min_p",
                     choices=["min_p", "greedy", "top_k", "top_p",
-                             "temperature"])
+                             "temperature", "chain"],
+                    help="chain: --top-k, then --top-p, then --min-p "
+                         "together (0 / 1 / 0 switch a filter off)")
     ap.add_argument("--min-p", type=float, default=0.1)
+    ap.add_argument("--top-k", type=int, default=50)
+    ap.add_argument("--top-p", type=float, default=0.9)
     ap.add_argument("--temperature", type=float, default=1.0)
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--max-seq", type=int, default=4096)
@@ -75,7 +79,8 @@ def main(argv=None):
               f"perplexity {res.perplexity:.4f}")
         return
     params = L.SamplingParams(strategy=args.strategy, min_p=args.min_p,
-                              temperature=args.temperature, seed=args.seed)
+                              temperature=args.temperature, seed=args.seed,
+                              top_k=args.top_k, top_p=args.top_p)
     t0 = time.time()
     if args.draft is not None:
         _, draft, _ = L.load_model(args.draft, backend=args.backend,

@@ -34,22 +34,29 @@ class SampleSpec:
     proc: bool = False          # logit-adjust stage ahead of the sampler
     logprobs: bool = False      # logprob scan / commit around it
     rows: Optional[frozenset] = None   # modes of a row_sampler run
+    # what composed rows among ``rows`` add to the launch sequence
+    # (``hip_ops.SAMP_CHAIN_*`` bits: 1 the phase-2 select passes, 2 the
+    # min-p cut in the pick); 0: the launches of the modes alone
+    chain: int = 0
 
     def graph_key(self, kind: str, B: Optional[int] = None) -> tuple:
         """Key of the captured graph that serves this spec.  ``kind``:
         ``"decode"`` (single sequence), ``"decode_batch"`` or
         ``"decode_rows"`` (B lockstep rows).  Sampler values are part of
         a legacy key (they are launch arguments) and of no rows key (they
-        are device data); neither holds the logprob top-N."""
+        are device data); neither holds the logprob top-N.  A composed
+        rows spec appends ``"chain<bits>"``; every other key is
+        unchanged."""
         values = (self.greedy, self.min_p, self.temperature, self.top_k,
                   self.top_p)
         if kind == "decode_batch":
             key = ("batch", B) + values
         elif self.rows is not None:
             staged = rows_key(self.rows) + (self.proc,)
+            chain = (f"chain{int(self.chain)}",) if self.chain else ()
             if kind == "decode_rows":
-                return ("batchr", B) + staged + (self.logprobs,)
-            key = ("rows",) + staged
+                return ("batchr", B) + staged + (self.logprobs,) + chain
+            key = ("rows",) + staged + chain
         elif kind == "decode_rows":
             key = ("batchc", B) + values + (self.proc,)
         else:

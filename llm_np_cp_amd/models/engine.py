@@ -46,8 +46,9 @@ class DeviceCacheHandle:
 class GPUModel:
     # sampling strategies the in-graph device sampler implements; the
     # runtime (generate(), the server's batch scheduler) routes on this
+    # ("chain" is served through ``row_sampler`` only)
     device_strategies = frozenset(
-        {"greedy", "min_p", "top_k", "top_p", "temperature"})
+        {"greedy", "min_p", "top_k", "top_p", "temperature", "chain"})
     # logit processors the in-graph logit-adjust stage applies (set per
     # instance: everything at world == 1, nothing under tensor parallel)
     device_processors = frozenset()
@@ -141,8 +142,14 @@ class GPUModel:
         # requests that came without a seed of their own
         self._samp_modes = {}
         self._req_serial = 0
+        # slot -> ``ho.samp_row_chain`` bits of every composed row (a
+        # second filter beside its mode's): what the sampler launches on
+        # top of the modes while such a row is present
+        self._samp_chain = {}
         # mode set of the single-sequence table row (all zero = greedy)
+        # and that row's chain bits
         self._s_rows = frozenset({0})
+        self._s_chain = 0
         # host mirrors of len_buf / bt_lens (overflow guards) and the
         # number of lockstep rows in use
         self._host_len = 0
@@ -1208,6 +1215,13 @@ class GPUModel:
                              f"prefill_row(row_sampler=...)")
         return frozenset(self._samp_modes[b] for b in range(B))
 
+    def _row_chain(self, B: int) -> int:
+        """Chain bits of lockstep rows [0, B), ORed (host mirror)."""
+        bits = 0
+        for b in range(B):
+            bits |= self._samp_chain.get(b, 0)
+        return bits
+
     def _stage_setup(self, n: int, proc: bool, logprobs: bool,
                      lp_batch: bool):
         """State of the stages an ``n``-token decode call switches on:
@@ -1258,7 +1272,7 @@ class GPUModel:
         else:
             ho.sample_rows(logits, v.samp, v.gmax, v.pick, v.cnt,
                            v.next_token, v.ring, v.nout, v.lens, v.sel, B,
-                           not first, spec.rows)
+                           not first, spec.rows, chain=spec.chain)
         if spec.logprobs:
             ho.logprob_commit(logits, self.lp_cfg[sl], self.lp_stage[sl],
                               v.next_token, v.nout, self.lp_val[sl],
@@ -1307,6 +1321,7 @@ class GPUModel:
         if row_sampler is not None:
             words, mode = self._samp_pack(row_sampler)
             self._s_rows = frozenset({mode})
+            self._s_chain = ho.samp_row_chain(words.numpy())
             rskw = {"row_sampler": True}
         t0 = _time.perf_counter()
         with trace_range("prefill"):
@@ -1830,16 +1845,21 @@ class GPUModel:
         self.bt_lens[b:b + 1].fill_(P)
         self.bt_nout[b:b + 1].zero_()
         rb = slice(b, b + 1)
+        self._samp_chain.pop(b, None)
         if row_sampler is not None:
             self.bt_samp[b].copy_(samp_words)
             self._samp_modes[b] = samp_mode
+            bits = ho.samp_row_chain(samp_words.numpy())
+            if bits:
+                self._samp_chain[b] = bits
         else:
             self._samp_modes.pop(b, None)
         spec = SampleSpec(greedy, min_p, temperature, top_k, top_p,
                           proc=processors is not None,
                           logprobs=logprobs is not None,
                           rows=(frozenset({samp_mode})
-                                if row_sampler is not None else None))
+                                if row_sampler is not None else None),
+                          chain=self._samp_chain.get(b, 0))
         self._stage_setup(1, spec.proc, spec.logprobs, lp_batch=True)
         if spec.logprobs:
             self.setup_logprobs(b, logprobs)
@@ -1880,6 +1900,9 @@ class GPUModel:
             self._samp_modes[dst] = self._samp_modes[src]
         else:
             self._samp_modes.pop(dst, None)
+        self._samp_chain.pop(dst, None)
+        if src in self._samp_chain:
+            self._samp_chain[dst] = self._samp_chain[src]
         if src in self._proc_rows:
             # the row's history and settings travel with it (the 4·V-byte
             # bias row only when it has one); rows without processors
@@ -1930,7 +1953,8 @@ class GPUModel:
             self._host_lens[b] += n
         spec = SampleSpec(greedy, min_p, temperature, top_k, top_p,
                           processors, logprobs,
-                          self._row_modes(B) if row_sampler else None)
+                          self._row_modes(B) if row_sampler else None,
+                          self._row_chain(B) if row_sampler else 0)
         key = spec.graph_key("decode_rows", B)
         step = partial(self._batch_step, B, spec)
         g = self._bgraphs.get(key)
@@ -1969,12 +1993,14 @@ class GPUModel:
     def capture_decode_graph(self, greedy: bool = True, min_p: float = 0.1,
                              temperature: float = 1.0, top_k: int = 0,
                              top_p: float = 1.0, processors: bool = False,
-                             logprobs: bool = False, rows=None):
+                             logprobs: bool = False, rows=None,
+                             chain: int = 0):
         """Capture one decode step into a hipGraph (fixed shapes: KV pool
         is preallocated and the position is a device scalar — SURVEY §7
         'graph must be shape-stable').  ``logprobs``: the step carries the
         logprob stage (scan ahead of the adjust stage, commit after the
-        sampler).  ``rows``: the mode set of a ``row_sampler`` run.  The
+        sampler).  ``rows``: the mode set of a ``row_sampler`` run,
+        ``chain``: its row's chain bits (``ho.samp_row_chain``).  The
         arguments make a ``SampleSpec``; its ``graph_key`` is the mode the
         single graph slot is cached under.
 
@@ -1987,7 +2013,8 @@ class GPUModel:
         (no further capture attempts) and the exception is kept in
         ``self._graph_error``."""
         spec = SampleSpec(greedy, min_p, temperature, top_k, top_p,
-                          bool(processors), bool(logprobs), rows)
+                          bool(processors), bool(logprobs), rows,
+                          int(chain))
         # the stages are part of the key; the logprob top-N and, with
         # rows, the sampler values are not (device data)
         mode = spec.graph_key("decode")
@@ -2066,7 +2093,8 @@ class GPUModel:
         / top_k / top_p are then unused)."""
         spec = SampleSpec(greedy, min_p, temperature, top_k, top_p,
                           bool(processors), bool(logprobs),
-                          self._s_rows if row_sampler else None)
+                          self._s_rows if row_sampler else None,
+                          self._s_chain if row_sampler else 0)
         self._stage_setup(n_tokens, spec.proc, spec.logprobs, lp_batch=False)
         if self._host_len + n_tokens > self.max_seq:
             raise ValueError(
@@ -2082,7 +2110,7 @@ class GPUModel:
             # even when capture fails, so n_steps stays exact either way
             taken, ok = self.capture_decode_graph(
                 greedy, min_p, temperature, top_k, top_p, spec.proc,
-                spec.logprobs, spec.rows)
+                spec.logprobs, spec.rows, spec.chain)
             n_steps -= taken
             if not ok:
                 use_graph = False

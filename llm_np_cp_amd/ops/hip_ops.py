@@ -73,7 +73,7 @@ _SIGS = {
                           ctypes.c_void_p, ctypes.c_void_p],
     "launch_sample_rows": [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                            ctypes.c_int, ctypes.c_long, ctypes.c_void_p,
-                           ctypes.c_int, ctypes.c_int] +
+                           ctypes.c_int, ctypes.c_int, ctypes.c_int] +
                           [ctypes.c_void_p] * 7 +
                           [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p],
     "launch_logit_adjust": [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
@@ -477,6 +477,11 @@ def samp_row(params, seed: int, V: int) -> np.ndarray:
     the ``SamplingParams`` defaults).  The rules are those of
     ``sampling.device_sampler_kwargs``: ``temperature`` and ``top_p`` >= 1
     are the min-p mode with an empty cut, ``top_k`` is clamped to ``V``.
+    ``strategy="chain"`` composes top-k -> top-p -> min-p
+    (``sampling.filter_probs``): ``top_k`` <= 0 or >= ``V``, ``top_p`` >= 1
+    and ``min_p`` <= 0 switch their filter off; the row takes mode 2 if
+    top-k is on, else 3 if top-p is on, else 1, and the remaining filters
+    travel in the ``top_p`` / ``min_p`` words (``samp_row_chain``).
     The values are device data the kernels cannot report on, so they are
     checked here (as ``sample`` checks its arguments)."""
     V = int(V)
@@ -508,6 +513,22 @@ def samp_row(params, seed: int, V: int) -> np.ndarray:
             raise ValueError(f"top_p must be > 0, got {top_p}")
         top_p = min(1.0, top_p)
         mode = SAMP_TOP_P if top_p < 1.0 else SAMP_MIN_P
+    elif strategy == "chain":
+        # top-k -> top-p -> min-p, each with its own "off" value; the mode
+        # is the first filter that is on, the later ones ride in the value
+        # words the kernels read in modes 2 / 3
+        top_k = int(params.get("top_k", 50))
+        top_k = 0 if top_k <= 0 or top_k >= V else top_k  # >= V keeps all
+        top_p = float(params.get("top_p", 0.9))
+        if not 0.0 < top_p:
+            raise ValueError(f"top_p must be > 0, got {top_p}")
+        top_p = min(1.0, top_p)
+        min_p = float(params.get("min_p", 0.1))
+        if not min_p <= 1.0:
+            raise ValueError(f"min_p must be <= 1, got {min_p}")
+        min_p = max(0.0, min_p)
+        mode = (SAMP_TOP_K if top_k > 0 else
+                SAMP_TOP_P if top_p < 1.0 else SAMP_MIN_P)
     else:
         raise ValueError(f"unknown sampling strategy {strategy!r}")
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
@@ -522,12 +543,34 @@ def samp_row(params, seed: int, V: int) -> np.ndarray:
     return row
 
 
+# what a composed row asks of the launch sequence beyond its mode (bits)
+SAMP_CHAIN_TOP_P = 1  # top-k row with top_p < 1: the second select phase
+SAMP_CHAIN_MIN_P = 2  # top-k / top-p row with min_p > 0: min-p cut in the pick
+
+
+def samp_row_chain(row) -> int:
+    """Bits a packed table row adds to ``sample_rows(chain=...)``:
+    ``SAMP_CHAIN_TOP_P`` for a top-k row (mode 2) that also carries
+    ``top_p`` < 1, ``SAMP_CHAIN_MIN_P`` for a top-k / top-p row (mode 2 /
+    3) that also carries ``min_p`` > 0; 0 for every row of a single
+    filter.  The caller ORs them over the rows present."""
+    row = np.asarray(row).view(np.uint32)
+    mode = int(row[0])
+    min_p, top_p = (float(x) for x in row[[2, 4]].view(np.float32))
+    bits = 0
+    if mode == SAMP_TOP_K and top_p < 1.0:
+        bits |= SAMP_CHAIN_TOP_P
+    if mode in (SAMP_TOP_K, SAMP_TOP_P) and min_p > 0.0:
+        bits |= SAMP_CHAIN_MIN_P
+    return bits
+
+
 def sample_rows(logits: torch.Tensor, samp: torch.Tensor,
                 gmax: torch.Tensor, pick: torch.Tensor, cnt: torch.Tensor,
                 next_token: torch.Tensor, out_ring: torch.Tensor,
                 nout: torch.Tensor, len_ptr: torch.Tensor,
                 sel: torch.Tensor | None, batch: int, bump_len: bool,
-                modes):
+                modes, *, chain: int = 0):
     """``sample`` with every parameter read per row from ``samp`` (int32
     [>=batch, SAMP_WORDS], rows packed by ``samp_row``): rows of different
     strategies, temperatures and seeds share one launch sequence.  Row b's
@@ -536,6 +579,11 @@ def sample_rows(logits: torch.Tensor, samp: torch.Tensor,
     knowledge of the table; only the stages it needs are launched (all
     greedy: the ``sample(greedy=True)`` launch itself; no top-k / top-p
     row: max + pick; else max + select passes + pick, ``sel`` required).
+    ``chain``: the ``samp_row_chain`` bits of the rows present, ORed —
+    ``SAMP_CHAIN_TOP_P`` adds the phase-2 select passes between select and
+    pick, ``SAMP_CHAIN_MIN_P`` picks with the variant that reads the rows'
+    min-p word; 0 (the default) launches exactly what the modes alone
+    need, and a composed row would then keep its first cut only.
     Scratch (gmax / pick / cnt / sel) as for ``sample``."""
     modes = frozenset(int(m) for m in modes)
     if not modes or not modes <= {SAMP_GREEDY, SAMP_MIN_P, SAMP_TOP_K,
@@ -571,6 +619,15 @@ def sample_rows(logits: torch.Tensor, samp: torch.Tensor,
         raise ValueError("out_ring must be contiguous int32, one row per "
                          "batch row")
     any_select = bool(modes & {SAMP_TOP_K, SAMP_TOP_P})
+    chain = int(chain)
+    if not 0 <= chain <= 3:
+        raise ValueError(f"chain must be a combination of SAMP_CHAIN_TOP_P "
+                         f"and SAMP_CHAIN_MIN_P, got {chain}")
+    if (chain & SAMP_CHAIN_TOP_P and SAMP_TOP_K not in modes) \
+            or (chain and not any_select):
+        raise ValueError("chain bits need their row in `modes`: a top-k "
+                         "row for SAMP_CHAIN_TOP_P, a top-k / top-p row "
+                         "for SAMP_CHAIN_MIN_P")
     if any_select and (sel is None or sel.dtype != torch.int64
                        or not sel.is_contiguous()
                        or sel.numel() < batch * SAMPLE_SEL_WORDS):
@@ -581,7 +638,8 @@ def sample_rows(logits: torch.Tensor, samp: torch.Tensor,
     _check(lib().launch_sample_rows(
         _ptr(logits), V, lbf16, batch, ctypes.c_long(ring_stride),
         _ptr(samp), 1 if modes - {SAMP_GREEDY} else 0,
-        1 if any_select else 0, _ptr(gmax), _ptr(pick), _ptr(cnt),
+        1 if any_select else 0, chain, _ptr(gmax), _ptr(pick),
+        _ptr(cnt),
         _ptr(next_token), _ptr(out_ring), _ptr(nout), _ptr(len_ptr),
         1 if bump_len else 0, _ptr(sel), _stream()), "sample_rows")
 

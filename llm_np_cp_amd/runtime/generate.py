@@ -166,7 +166,9 @@ def generate(prompt: str, tokenizer, model, max_tokens: int = 200,
     that advertises ``device_row_sampler``, on the GPU fast path too:
     the request's settings and seed are per-row device data
     (``generate_tokens(..., row_sampler=...)``), and the same seed gives
-    the same tokens.  Without a seed — or on an engine without that
+    the same tokens.  ``strategy="chain"`` takes the fast path only on
+    such an engine (and only when it lists ``"chain"``), seeded or not;
+    elsewhere it runs the host loop.  Without a seed — or on an engine without that
     capability, e.g. under tensor parallelism — the fast path's sampler
     derives its stream from the ENGINE seed + a device counter."""
     params = params or SamplingParams()
@@ -213,7 +215,10 @@ def generate(prompt: str, tokenizer, model, max_tokens: int = 200,
                 getattr(model, "device_processors", ()))
             and hasattr(model, "generate_tokens")
             and params.strategy in getattr(model, "device_strategies",
-                                           ("greedy", "min_p"))):
+                                           ("greedy", "min_p"))
+            # the composed cut exists on the per-row sampler only
+            and (params.strategy != "chain"
+                 or getattr(model, "device_row_sampler", False))):
         t0 = time.perf_counter()
 
         def _emit(ids_chunk):
@@ -228,10 +233,11 @@ def generate(prompt: str, tokenizer, model, max_tokens: int = 200,
 
         # a seeded request on an engine whose sampler reads its settings
         # per row from device memory: the seed travels with them, and the
-        # stream is a function of it alone
+        # stream is a function of it alone; a chain request always goes
+        # that way (seed None: the engine derives one per request)
         rs_kw = {}
-        if params.seed is not None and getattr(model, "device_row_sampler",
-                                               False):
+        if (params.seed is not None or params.strategy == "chain") \
+                and getattr(model, "device_row_sampler", False):
             rs_kw["row_sampler"] = device_row_sampler_kwargs(params)
 
         ids = model.generate_tokens(

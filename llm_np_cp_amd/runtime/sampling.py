@@ -18,7 +18,11 @@ import numpy as np
 
 @dataclass
 class SamplingParams:
-    strategy: str = "min_p"   # "min_p" | "greedy" | "top_k" | "top_p" | "temperature"
+    # "min_p" | "greedy" | "top_k" | "top_p" | "temperature" | "chain".
+    # "chain" applies top_k, then top_p, then min_p together (each has an
+    # "off" value: top_k <= 0, top_p >= 1, min_p <= 0); with the defaults
+    # below all three are on.  Every other strategy reads its own field only.
+    strategy: str = "min_p"
     min_p: float = 0.1
     temperature: float = 1.0
     top_k: int = 50
@@ -144,9 +148,39 @@ def filter_probs(logits: np.ndarray, params: SamplingParams,
         mask = np.zeros_like(probs, dtype=bool)
         mask[order[:cutoff]] = True
         probs = np.where(mask, probs, 0.0)
+    elif params.strategy == "chain":
+        probs = _chain_filter(probs, params)
     elif params.strategy != "temperature":
         raise ValueError(f"unknown sampling strategy {params.strategy!r}")
     return probs / probs.sum()
+
+
+def _chain_filter(probs: np.ndarray, params: SamplingParams) -> np.ndarray:
+    """top-k -> top-p (over the renormalised top-k survivors) -> min-p on
+    a softmax vector; each step is the single-filter branch of
+    ``filter_probs`` on what the step before kept, so a chain with one
+    filter on is that strategy's vector.  Not renormalised."""
+    if not 0.0 < params.top_p:
+        raise ValueError(f"top_p must be > 0, got {params.top_p}")
+    if not params.min_p <= 1.0:
+        raise ValueError(f"min_p must be <= 1, got {params.min_p}")
+    p_max = probs.max()
+    k_on = 0 < params.top_k < len(probs)  # k >= V keeps the whole row
+    if k_on:
+        thresh = np.partition(probs, -params.top_k)[-params.top_k]
+        probs = np.where(probs >= thresh, probs, 0.0)
+    if params.top_p < 1.0:
+        renorm = probs / probs.sum() if k_on else probs
+        order = np.argsort(-renorm)
+        csum = np.cumsum(renorm[order])
+        cutoff = np.searchsorted(csum, params.top_p) + 1
+        mask = np.zeros_like(probs, dtype=bool)
+        mask[order[:cutoff]] = True
+        probs = np.where(mask, probs, 0.0)
+    if params.min_p > 0.0:
+        # p_max survives both steps above, so the cut is that of "min_p"
+        probs = np.where(probs >= params.min_p * p_max, probs, 0.0)
+    return probs
 
 
 def device_sampler_kwargs(params: SamplingParams) -> dict:
@@ -180,6 +214,10 @@ def device_sampler_kwargs(params: SamplingParams) -> dict:
         if not 0.0 < params.top_p:
             raise ValueError(f"top_p must be > 0, got {params.top_p}")
         kw["top_p"] = min(1.0, float(params.top_p))
+    elif params.strategy == "chain":
+        # composed cuts exist on the per-row sampler only: the legacy
+        # values are not used when a ``row_sampler`` goes with them
+        pass
     elif params.strategy != "temperature":
         raise ValueError(f"unknown sampling strategy {params.strategy!r}")
     return kw
@@ -193,7 +231,10 @@ def device_row_sampler_kwargs(params: SamplingParams) -> dict:
     as ``device_sampler_kwargs``: ``temperature`` and ``top_p`` >= 1 are a
     min-p cut with ``min_p = 0`` (the whole vocabulary stays), ``top_k``
     is at least 1 (the engine clamps it to the vocabulary).  ``seed`` is
-    the request's seed (None: the engine derives one per request)."""
+    the request's seed (None: the engine derives one per request).
+    ``"chain"`` carries all three filter values with the off-rules
+    applied: ``top_k`` 0 = off (the engine also treats >= vocabulary as
+    off), ``top_p`` 1.0 = off, ``min_p`` 0.0 = off."""
     kw = dict(strategy=params.strategy,
               temperature=float(params.temperature), seed=params.seed)
     if params.strategy == "min_p":
@@ -209,6 +250,14 @@ def device_row_sampler_kwargs(params: SamplingParams) -> dict:
             kw["top_p"] = float(params.top_p)
     elif params.strategy == "temperature":
         kw.update(strategy="min_p", min_p=0.0)
+    elif params.strategy == "chain":
+        if not 0.0 < params.top_p:
+            raise ValueError(f"top_p must be > 0, got {params.top_p}")
+        if not params.min_p <= 1.0:
+            raise ValueError(f"min_p must be <= 1, got {params.min_p}")
+        kw.update(top_k=max(0, int(params.top_k)),
+                  top_p=min(1.0, float(params.top_p)),
+                  min_p=max(0.0, float(params.min_p)))
     elif params.strategy != "greedy":
         raise ValueError(f"unknown sampling strategy {params.strategy!r}")
     return kw

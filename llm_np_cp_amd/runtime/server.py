@@ -42,7 +42,10 @@ try:  # pydantic model must live at module scope (ForwardRef resolution)
 
     from pydantic import BaseModel, Field, model_validator
 
-    _Strategy = Literal["min_p", "greedy", "top_k", "top_p", "temperature"]
+    # "chain": top_k, top_p and min_p together (a top_k at or above the
+    # vocabulary size, top_p = 1 and min_p = 0 switch their filter off)
+    _Strategy = Literal["min_p", "greedy", "top_k", "top_p", "temperature",
+                        "chain"]
 
     class CompletionRequest(BaseModel):
         prompt: str
@@ -226,6 +229,8 @@ class BatchScheduler:
         # lockstep group only surfaces ids per chunk
         return (self.max_batch > 1
                 and req.strategy in self.device_strategies
+                # composed filters exist on the per-row sampler only
+                and (req.strategy != "chain" or self.device_row_sampler)
                 and not getattr(req, "stream", False)
                 and not getattr(req, "stop", None)
                 and self._logprobs_ok(getattr(req, "logprobs", None))

@@ -131,6 +131,74 @@ def main():
     print(f"sample top-p  V={V}: {us:.2f}us")
 
 
+def sampler_rows():
+    """The per-row sampler call (``sample_rows``), one uniform group per
+    line: today's four modes and the composed top-k -> top-p (-> min-p)
+    rows, V = 128256 / 256000, B = 1 fp32 and B = 8 bf16 rows of 2*randn
+    logits.  Median of 5 ``time_graph`` measurements, us per sampler call.
+    A build that does not know a strategy prints "-" for it, so the same
+    file measures an older checkout (profiles/sampler_chain.md)."""
+    import numpy as np
+
+    from csrc.build import ensure_built
+    ensure_built()
+    from llm_np_cp_amd.ops import hip_ops as ho
+
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    groups = [
+        ("greedy", dict(strategy="greedy")),
+        ("min-p 0.1", dict(strategy="min_p", min_p=0.1)),
+        ("top-k 50", dict(strategy="top_k", top_k=50)),
+        ("top-p 0.9", dict(strategy="top_p", top_p=0.9)),
+        ("chain 50/.9/0", dict(strategy="chain", top_k=50, top_p=0.9,
+                               min_p=0.0)),
+        ("chain 50/.9/.1", dict(strategy="chain", top_k=50, top_p=0.9,
+                                min_p=0.1)),
+    ]
+    i64 = dict(dtype=torch.int64, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    for V in (128256, 256000):
+        for B, dt in ((1, torch.float32), (8, torch.bfloat16)):
+            g = torch.Generator().manual_seed(V + B)
+            logits = (2.0 * torch.randn(B, V, generator=g)).to(dev, dt)
+            lg = logits if B > 1 else logits[0]
+            gmax, pick = torch.zeros(B, **i64), torch.zeros(B, **i64)
+            cnt, nt_ = torch.zeros(B, **i32), torch.zeros(B, **i32)
+            ring = torch.zeros(B, 65536, **i32) if B > 1 else \
+                torch.zeros(65536, **i32)
+            nout, ln = torch.zeros(B, **i32), torch.zeros(B, **i32)
+            sel = torch.zeros(B, ho.SAMPLE_SEL_WORDS, **i64)
+            samp = torch.zeros(B, ho.SAMP_WORDS, **i32)
+            for name, d in groups:
+                try:
+                    rows = [ho.samp_row(d, 1000 + b, V) for b in range(B)]
+                except ValueError:
+                    print(f"rows V={V} B={B} {name}: -")
+                    continue
+                samp.copy_(torch.from_numpy(
+                    np.stack(rows).view(np.int32)))
+                kw = {}
+                if hasattr(ho, "samp_row_chain"):
+                    kw["chain"] = ho.samp_row_chain(rows[0])
+                modes = {int(rows[0][0])}
+
+                def call():
+                    ho.sample_rows(lg, samp, gmax, pick, cnt, nt_, ring,
+                                   nout, ln, sel, B, False, modes, **kw)
+
+                us = []
+                for _ in range(5):
+                    nout.zero_()
+                    us.append(time_graph(call))
+                print(f"rows V={V} B={B} {name}: {sorted(us)[2]:.2f} "
+                      f"[{min(us):.2f}-{max(us):.2f}]")
+
+
+if __name__ == "__main__" and "--sampler-rows" in sys.argv:
+    sampler_rows()
+    sys.exit(0)
+
 if __name__ == "__main__" and "--layersim" not in sys.argv:
     main()
 
