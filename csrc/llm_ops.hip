@@ -4059,6 +4059,166 @@ extern "C" hipError_t launch_logprob_rows(const void* logits, int V,
 }
 
 // ====================================================================
+// Greedy speculative decoding, verify + commit: k_spec_verify reduces the
+// k+1 logits rows of a target verify pass to their argmax, finds the
+// accepted prefix of the k draft tokens and commits the outcome into the
+// device state of BOTH engines — the host sees no logit.
+//   logits  [k+1, V]  bf16 / fp32, contiguous rows; row i scores draft i,
+//                     row k is the bonus position
+//   drafts  [k]       i32 proposals (the target's ids_buf[1..k])
+//   scratch [SPEC_SCRATCH_WORDS] u64: [0..SPEC_MAX_K] packed (fkey, id) row
+//                     maxima, [SPEC_MAX_K + 1] the launch-wide ticket; all
+//                     zero between launches (zeroed once by the host, every
+//                     word a launch touched is re-armed by its commit)
+// Grid (blocks, k+1): the blocks of a row split it in LP_SLICE-wide slices
+// (thread t owns the 8 logits [s*2048 + 8t, +8) of a slice, loaded as in
+// k_logprob_rows), reduce to one packed word and atomicMax it into the
+// row's scratch word — ties go to the SMALLEST id, as k_logit_max and
+// np.argmax.  ONE ticket over the whole launch (release fence before the
+// add, acquire fence in the last arriver, as sample_pick_commit); thread 0
+// of the last-arriving block then commits:
+//   a_i = argmax of row i (outside [0, V): 0, the NaN-logit insurance)
+//   m   = the largest j <= k with drafts[i] == a_i for all i < j
+//   n   = *t_len — the verify pass leaves the target's length at the
+//         position it started from (_layers_forward reads it, nobody
+//         advances it), so the kernel reads n there and takes no argument
+//   target: out_ring[nout .. nout+m] = drafts[0..m-1], a_m; nout += m + 1;
+//           next_token = a_m; len = n + m + 1
+//   draft:  len = n + m + 1; next_token = a_m; nout = 0 (the next cycle's
+//           proposals land in its out_ring[0..k] again)
+//   rec[*nrec % rec_cap] = {m, drafts[0..k-1], -1 ...}; *nrec += 1
+// m <= k by construction, so no length above n + k + 1 is ever written;
+// ring writes past ring_cap are dropped.  Plain stores only.
+// ====================================================================
+#define SPEC_MAX_K 16
+#define SPEC_SCRATCH_WORDS (SPEC_MAX_K + 2)
+#define SPEC_REC_WORDS (SPEC_MAX_K + 1)
+#define SPEC_AUTO_BLOCKS 8
+
+template <bool BF>
+DEVINL uint64_t spec_slice_max(const void* logits, int V) {
+  const char* row =
+      (const char*)logits + (size_t)blockIdx.y * V * (BF ? 2 : 4);
+  const bool al = ((uintptr_t)row & 15) == 0;
+  float mv = -INFINITY;
+  int mi = 0x7fffffff;  // nothing seen: loses every tie, clamped if it wins
+  const long step = (long)gridDim.x * LP_SLICE;
+  for (long base = (long)blockIdx.x * LP_SLICE; base < V; base += step) {
+    const int i0 = (int)base + threadIdx.x * 8;
+    if (i0 >= V) continue;
+    float x[8];
+    lpr_load8<BF>(row, i0, V, al, x);
+    // ascending ids: a strict > keeps the smallest id of equal values
+#pragma unroll
+    for (int j = 0; j < 8; j++)
+      if (i0 + j < V && x[j] > mv) { mv = x[j]; mi = i0 + j; }
+  }
+  return pack_ki(fkey(mv), mi);
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+k_spec_verify(const void* __restrict__ logits, int V, int lbf16, int k,
+              const int* drafts, unsigned long long* scratch,
+              int* t_len, int* t_next, int* t_ring, int* t_nout, int ring_cap,
+              int* d_len, int* d_next, int* d_nout,
+              int* rec, int* nrec, int rec_cap) {
+  uint64_t pk = lbf16 ? spec_slice_max<true>(logits, V)
+                      : spec_slice_max<false>(logits, V);
+#pragma unroll
+  for (int w = 1; w < 64; w <<= 1) {
+    uint64_t o = __shfl_xor((unsigned long long)pk, w);
+    if (o > pk) pk = o;
+  }
+  __shared__ unsigned long long ws[4];
+  __shared__ int lastflag;
+  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = pk;
+  __syncthreads();
+  int* ticket = (int*)(scratch + SPEC_MAX_K + 1);
+  if (threadIdx.x == 0) {
+    uint64_t b = ws[0];
+    for (int w = 1; w < 4; w++) if (ws[w] > b) b = ws[w];
+    atomicMax(scratch + blockIdx.y, (unsigned long long)b);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    int t = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_ACQ_REL,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+    lastflag = (t == (int)(gridDim.x * gridDim.y) - 1);
+  }
+  __syncthreads();
+  if (!lastflag || threadIdx.x != 0) return;
+  // last arriver: every row's maximum is in; commit and re-arm
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  *ticket = 0;
+  if (k < 1) k = 1;
+  if (k > SPEC_MAX_K) k = SPEC_MAX_K;
+  int m = -1, am = 0;
+  for (int i = 0; i <= k; i++) {
+    int a = unpack_idx(__hip_atomic_load(scratch + i, __ATOMIC_RELAXED,
+                                         __HIP_MEMORY_SCOPE_AGENT));
+    scratch[i] = 0ull;
+    if (a < 0 || a >= V) a = 0;
+    if (m < 0 && (i == k || drafts[i] != a)) { m = i; am = a; }
+  }
+  const int n = *t_len;
+  const int no = *t_nout;
+  for (int j = 0; j <= m; j++) {
+    // accepted drafts equal an in-range argmax, so they are in [0, V)
+    const int tok = j < m ? drafts[j] : am;
+    if (no + j >= 0 && no + j < ring_cap) t_ring[no + j] = tok;
+  }
+  *t_nout = no + m + 1;
+  *t_next = am;
+  *t_len = n + m + 1;
+  *d_len = n + m + 1;
+  *d_next = am;
+  *d_nout = 0;
+  const int nr = *nrec;
+  int* r = rec + (size_t)((nr < 0 ? 0 : nr) % rec_cap) * SPEC_REC_WORDS;
+  r[0] = m;
+  for (int i = 0; i < SPEC_MAX_K; i++) r[1 + i] = i < k ? drafts[i] : -1;
+  *nrec = nr + 1;
+}
+
+// blocks <= 0: SPEC_AUTO_BLOCKS per row; never more than the row has slices
+extern "C" hipError_t launch_spec_verify(
+    const void* logits, int V, int lbf16, int rows, int k, int blocks,
+    const void* drafts, void* scratch, void* t_len, void* t_next,
+    void* t_ring, void* t_nout, int ring_cap, void* d_len, void* d_next,
+    void* d_nout, void* rec, void* nrec, int rec_cap, hipStream_t stream) {
+  if (k < 1 || k > SPEC_MAX_K || V <= 0 || V > (1 << 30) || rows != k + 1 ||
+      ring_cap <= 0 || rec_cap <= 0)
+    return hipErrorInvalidValue;
+  const int slices = (V + LP_SLICE - 1) / LP_SLICE;
+  if (blocks <= 0) blocks = SPEC_AUTO_BLOCKS;
+  if (blocks > slices) blocks = slices;
+  hipLaunchKernelGGL(k_spec_verify, dim3(blocks, rows), dim3(256), 0, stream,
+                     logits, V, lbf16, k, (const int*)drafts,
+                     (unsigned long long*)scratch, (int*)t_len, (int*)t_next,
+                     (int*)t_ring, (int*)t_nout, ring_cap, (int*)d_len,
+                     (int*)d_next, (int*)d_nout, (int*)rec, (int*)nrec,
+                     rec_cap);
+  return hipGetLastError();
+}
+
+// ids of a verify pass, on the stream: ids[0] = the target's pending token,
+// ids[1..k] = the draft's proposals (its out_ring[0..k-1]).  k = 0 stages
+// the pending token alone (a plain step through the verify pass).
+extern "C" __global__ void __launch_bounds__(64)
+k_spec_stage(int* ids, const int* t_next, const int* d_ring, int k) {
+  const int t = threadIdx.x;
+  if (t == 0) ids[0] = t_next[0];
+  else if (t <= k) ids[t] = d_ring[t - 1];
+}
+
+extern "C" hipError_t launch_spec_stage(void* ids, const void* t_next,
+                                        const void* d_ring, int k,
+                                        hipStream_t stream) {
+  if (k < 0 || k > SPEC_MAX_K) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_spec_stage, dim3(1), dim3(64), 0, stream, (int*)ids,
+                     (const int*)t_next, (const int*)d_ring, k);
+  return hipGetLastError();
+}
+
+// ====================================================================
 // Prefill GEMM: Y[M,N] = X[M,K] @ W[N,K]^T (+res), bf16 in/out, fp32 acc.
 // MFMA v_mfma_f32_16x16x32_bf16; 128x128 tile, BK=32, 4 waves (2x2),
 // each wave a 64x64 sub-tile (4x4 fragments).  LDS staged, padded rows.

@@ -60,6 +60,13 @@ class GPUModel:
     # sampler settings share one lockstep group and one captured graph,
     # and ``seed`` is honored (set per instance: True at world == 1)
     device_row_sampler = False
+    # greedy speculative decoding runs device-side with this engine as
+    # target or draft (``speculative_tokens``; set per instance: True at
+    # world == 1 without MoE)
+    device_speculative = False
+    # verify cycles a speculative chunk runs between two host reads
+    # (profiles/spec_device.md)
+    SPEC_CHUNK = 4
 
     def __init__(self, config: ModelConfig, weights: Dict[str, np.ndarray],
                  dtype: str = "bf16", max_seq: Optional[int] = 4096,
@@ -134,6 +141,10 @@ class GPUModel:
         self.device_prompt_logprobs = \
             ho.LOGPROBS_MAX_TOP if self.world == 1 else 0
         self.pl_logits = self.pl_tgt = self.pl_val = self.pl_idx = None
+        # speculative verify state (logits / scratch / record ring):
+        # allocated by the first verify pass
+        self.device_speculative = self.world == 1 and not self.moe
+        self.sp_logits = self.sp_scratch = self.sp_rec = self.sp_nrec = None
         if self.world == 1:
             self.device_row_sampler = True
         # host mirror of the per-row sampler table: slot -> mode of every
@@ -1039,6 +1050,221 @@ class GPUModel:
             raise ValueError(f"rewind {n} outside [0, {self.max_seq}]")
         ho.i32_set(self.len_buf, n)
         self._host_len = n
+
+    # ------------------------------------------------------------------
+    # device-side greedy speculative decoding (this engine = the target)
+    # ------------------------------------------------------------------
+    # records a chunk can hold (its cycle count is capped to this)
+    SPEC_REC = 64
+
+    def _spec_alloc(self):
+        """State of the speculative verify pass, allocated by the first
+        call and kept: logits [SPEC_MAX_K+1, V] bf16, the verify kernel's
+        scratch (zeroed here once, re-armed on the device), the record
+        ring [SPEC_REC, 1+SPEC_MAX_K] i32 and its counter."""
+        assert self.device_speculative
+        if self.sp_logits is None:
+            dev = self.device
+            self.sp_logits = torch.zeros(
+                ho.SPEC_MAX_K + 1, self.config.vocab_size,
+                dtype=torch.bfloat16, device=dev)
+            self.sp_scratch = torch.zeros(ho.SPEC_SCRATCH_WORDS,
+                                          dtype=torch.int64, device=dev)
+            self.sp_rec = torch.zeros(self.SPEC_REC, ho.SPEC_REC_WORDS,
+                                      dtype=torch.int32, device=dev)
+            self.sp_nrec = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def decode_steps_async(self, n: int):
+        """``n`` greedy decode steps with no synchronise and no ring
+        read-back: replays of the greedy decode graph (captured here when
+        it is not there yet; its warm-up is one REAL step and counts as
+        one of the n), or eager steps when capture failed.  The
+        speculative draft loop; ``decode`` keeps its behaviour."""
+        if n < 1:
+            return
+        if self._host_len + n > self.max_seq:
+            raise ValueError(
+                f"decode would overflow the KV pool: len {self._host_len} "
+                f"+ {n} > max_seq {self.max_seq}")
+        self._host_len += n
+        taken, ok = self.capture_decode_graph()
+        n -= taken
+        if ok:
+            for _ in range(n):
+                self._graph.replay()
+        else:
+            spec = SampleSpec()
+            for _ in range(n):
+                self._step(spec)
+
+    def spec_verify_pass(self, draft: Optional["GPUModel"], k: int,
+                         blocks: int = 0):
+        """One verify pass of greedy speculative decoding on this engine,
+        nothing crossing to the host: stage [next_token, draft.out_ring[:k]]
+        into ids_buf, embed, the layer stack over k+1 rows from len_buf,
+        final norm, lm_head GEMM in the weight dtype into the kept
+        ``sp_logits`` rows, final softcap, then ``spec_verify`` commits the
+        accepted prefix and the target's own token into both engines'
+        state (docs/KERNELS.md).  ``k`` = 0 is a plain greedy step through
+        the same kernels (``draft`` unused, may be None): the sampling
+        tail commits row 0.  The caller guarantees len + k + 1 <= max_seq
+        on both engines."""
+        self._spec_alloc()
+        M = k + 1
+        ho.spec_stage(self.ids_buf, self.next_token,
+                      draft.out_ring if k else self.out_ring, k)
+        ho.embed(self.embed, self.ids_buf, self.b_h, M,
+                 self.config.embed_scale)
+        self._layers_forward(M)
+        ho.rmsnorm(self.b_h[:M], self.g_final, self.b_xn[:M],
+                   eps=self.config.rms_norm_eps)
+        y = self.sp_logits[:M]
+        if self.wq4:
+            ho.gemm_fp4w(self.b_xn[:M], self.lm_head_q4, self.lm_head_e4, y,
+                         accbuf=self.b_gemm_acc)
+        elif self.fp8:
+            ho.quant_fp8(self.b_xn[:M], self.b_xq, self.b_sx)
+            ho.gemm_fp8(self.b_xq, self.b_sx, self.lm_head_q,
+                        self.lm_head_s, y, M, self.H,
+                        accbuf=self.b_gemm_acc)
+        else:
+            ho.gemm(self.b_xn[:M], self.lm_head, y, accbuf=self.b_gemm_acc)
+        if self.final_softcap:
+            ho.softcap(y, self.final_softcap)
+        if k == 0:
+            self._sample_tail(y, self._sv, 1, SampleSpec())
+            return
+        ho.spec_verify(y, k, self.ids_buf[1:1 + k], self.sp_scratch,
+                       self.len_buf, self.next_token, self.out_ring,
+                       self.nout, draft.len_buf, draft.next_token,
+                       draft.nout, self.sp_rec, self.sp_nrec, blocks=blocks)
+
+    def spec_chunk(self, draft: "GPUModel", k: int, cycles: int,
+                   nout0: int):
+        """``cycles`` speculative cycles back to back, ONE synchronise at
+        the end.  A cycle: k+1 draft steps (the last one writes the KV of
+        the k-th proposal, so a fully accepted cycle leaves the draft
+        nothing to catch up on; its own proposal is dropped), one verify
+        pass, the commit.  ``k`` = 0: ``cycles`` plain target steps.
+        ``nout0``: the target's ring count before the chunk.  Returns
+        ``(ids, recs)``: the tokens emitted (int32 array) and, for k > 0,
+        one ``(m, drafts)`` per cycle; both engines' ``_host_len`` mirror
+        the device lengths afterwards.  The caller has checked that
+        len + cycles * (k+1) fits both pools."""
+        n = self._host_len
+        need = n + cycles * (k + 1)
+        if need > self.max_seq or (k and need > draft.max_seq):
+            raise ValueError(f"speculative chunk {n} + {cycles} x {k + 1} "
+                             f"exceeds a KV pool")
+        if not 1 <= cycles <= self.SPEC_REC:
+            raise ValueError(f"cycles must be within 1..{self.SPEC_REC}")
+        self._spec_alloc()
+        if k:
+            ho.i32_set(self.sp_nrec, 0)
+            draft._host_len = n
+        for _ in range(cycles):
+            if k:
+                draft.decode_steps_async(k + 1)
+            self.spec_verify_pass(draft, k)
+        scal = torch.cat([self.nout, self.len_buf,
+                          draft.len_buf if k else self.len_buf])
+        torch.cuda.synchronize()
+        nout, t_len, d_len = (int(v) for v in scal.cpu().numpy())
+        ids = self.out_ring[nout0:nout].cpu().numpy()
+        self._host_len = t_len
+        recs = []
+        if k:
+            draft._host_len = d_len
+            for row in self.sp_rec[:cycles].cpu().numpy():
+                recs.append((int(row[0]), [int(t) for t in row[1:1 + k]]))
+        return ids, recs
+
+    def speculative_tokens(self, draft: "GPUModel", prompt_ids,
+                           max_tokens: int, k: int = 4, eos_id=None,
+                           on_ids=None):
+        """Greedy decode of this engine (the target) accelerated by
+        ``draft``, device-side: the token stream is this engine's own
+        greedy chain under the verify pass's numerics.  Both engines are
+        prefilled with the prompt, the first token comes from the target's
+        prefill logits, then chunks of ``SPEC_CHUNK`` cycles run between two
+        host reads.  Before each chunk the cycle count, then k, shrink
+        until len + cycles * (k+1) fits both pools — the positions a chunk
+        writes at most, [len, len + cycles * (k+1)), so no slot of a pool
+        stays unused and the run ends where the host loop's ends; without
+        room for a draft the target takes plain steps until its pool is
+        full.  ``on_ids`` sees each chunk's new ids (cut at EOS and
+        at ``max_tokens``).  Returns ``(ids, recs)``: at most ``max_tokens``
+        ids, ending with the first EOS, and one ``(k, m, drafts)`` per
+        verify pass that ran (the passes of a chunk that follow an EOS
+        included)."""
+        import time as _time
+        if not (self.device_speculative
+                and getattr(draft, "device_speculative", False)):
+            raise ValueError("device-side speculative decoding needs "
+                             "single-GPU, non-MoE GPUModel engines")
+        if draft is self:
+            raise ValueError("draft and target must be two engines")
+        if draft.device != self.device:
+            raise ValueError(f"draft on {draft.device}, target on "
+                             f"{self.device}: the engines must share a device")
+        if draft.config.vocab_size != self.config.vocab_size:
+            raise ValueError(
+                f"draft vocabulary {draft.config.vocab_size} != target "
+                f"vocabulary {self.config.vocab_size}")
+        if not 1 <= k <= ho.SPEC_MAX_K:
+            raise ValueError(f"k must be within 1..{ho.SPEC_MAX_K}, got {k}")
+        prompt_ids = np.asarray(prompt_ids, dtype=np.int32).ravel()
+        P0 = len(prompt_ids)
+        pool = min(self.max_seq, draft.max_seq)
+        if P0 + 1 > pool:
+            raise ValueError(f"prompt {P0} fills the KV pool ({pool})")
+        eos_set = (set() if eos_id is None else
+                   {int(eos_id)} if np.isscalar(eos_id) else
+                   {int(e) for e in eos_id})
+        C = max(1, min(int(self.SPEC_CHUNK), self.SPEC_REC))
+        t0 = _time.perf_counter()
+        with trace_range("prefill"):
+            self._pb = draft._pb = 0
+            self.prefill(prompt_ids)
+            draft.prefill(prompt_ids)
+            # first token: greedy tail on the prefill logits (no length
+            # bump), handed to the draft as its pending token
+            self._sample_tail(self.b_logits, self._sv, 1, SampleSpec(),
+                              first=True)
+            draft.next_token.copy_(self.next_token)
+            draft.nout.zero_()
+            torch.cuda.synchronize()
+            out = [int(self.out_ring[0].item())]
+        self.last_prefill_time_s = _time.perf_counter() - t0
+        if on_ids:
+            on_ids(out[:max_tokens])
+        recs = []
+        with trace_range("decode"):
+            while len(out) < max_tokens and out[-1] not in eos_set:
+                n = self._host_len
+                kk = min(k, self.max_seq - n - 1, draft.max_seq - n - 1)
+                left = max_tokens - len(out)
+                if kk < 1:
+                    if n + 1 >= self.max_seq:
+                        break                 # target pool exhausted
+                    kk = 0
+                    c = min(C, left, self.max_seq - 1 - n)
+                else:
+                    # no more cycles than full acceptance would need: no
+                    # pass ever starts past the budget, as in the host loop
+                    c = min(C, -(-left // (kk + 1)), (pool - n) // (kk + 1))
+                ids, rr = self.spec_chunk(draft, kk, c, len(out))
+                recs.extend((kk, m, d) for m, d in rr)
+                take = [int(t) for t in ids][:left]
+                hit = [j for j, t in enumerate(take) if t in eos_set]
+                if hit:
+                    take = take[:hit[0] + 1]
+                out.extend(take)
+                if on_ids and take:
+                    on_ids(take)
+                if hit:
+                    break
+        return out[:max_tokens], recs
 
     def forward_hf(self, ids: np.ndarray):
         """Reference-parity output tuple ``(loss, logits, kv_cache,

@@ -89,6 +89,12 @@ _SIGS = {
     "launch_logprob_rows": [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                             ctypes.c_int, ctypes.c_void_p, ctypes.c_int] +
                            [ctypes.c_void_p] * 3,
+    "launch_spec_verify": [ctypes.c_void_p] + [ctypes.c_int] * 5 +
+                          [ctypes.c_void_p] * 6 + [ctypes.c_int] +
+                          [ctypes.c_void_p] * 5 + [ctypes.c_int,
+                                                   ctypes.c_void_p],
+    "launch_spec_stage": [ctypes.c_void_p] * 3 + [ctypes.c_int,
+                                                  ctypes.c_void_p],
     "launch_gemm_bf16": [ctypes.c_void_p] * 5 + [ctypes.c_int] * 3 +
                         [ctypes.c_void_p],
     "launch_softcap": [ctypes.c_void_p, ctypes.c_long, ctypes.c_float,
@@ -857,6 +863,98 @@ def logprob_rows(logits: torch.Tensor, targets: torch.Tensor, top_n: int,
         _ptr(logits), V, 1 if logits.dtype == torch.bfloat16 else 0, M,
         _ptr(targets), top_n, _ptr(val), _ptr(idx), _stream()),
         "logprob_rows")
+
+
+# greedy speculative verify (csrc/llm_ops.hip SPEC_*): most drafts per
+# verify pass, u64 scratch words (row maxima + ticket), int32 words of one
+# record {m, drafts[SPEC_MAX_K]}
+SPEC_MAX_K = 16
+SPEC_SCRATCH_WORDS = SPEC_MAX_K + 2
+SPEC_REC_WORDS = SPEC_MAX_K + 1
+
+
+def _spec_i32(name: str, t: torch.Tensor, n: int, dev):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 \
+            or not t.is_contiguous() or t.numel() < n:
+        raise ValueError(f"{name} must be a contiguous int32 tensor of at "
+                         f"least {n} element(s)")
+    if t.device != dev:
+        raise ValueError(f"{name} must live on the logits' device")
+
+
+def spec_verify(logits: torch.Tensor, k: int, drafts: torch.Tensor,
+                scratch: torch.Tensor, t_len: torch.Tensor,
+                t_next: torch.Tensor, t_ring: torch.Tensor,
+                t_nout: torch.Tensor, d_len: torch.Tensor,
+                d_next: torch.Tensor, d_nout: torch.Tensor,
+                rec: torch.Tensor, nrec: torch.Tensor, blocks: int = 0):
+    """Greedy speculative verify + commit, all on the device.  ``logits``
+    (fp32 or bf16 [k+1, V], contiguous) are the target's rows for the
+    pending token and the ``k`` ``drafts`` (int32 [>=k]).  Row i's argmax
+    a_i (ties: smallest id) is compared with ``drafts[i]``; with m the
+    length of the matching prefix, the tokens ``drafts[:m] + [a_m]`` are
+    appended to ``t_ring`` at ``t_nout`` (``t_nout += m + 1``),
+    ``t_next = d_next = a_m``, ``t_len = d_len = n + m + 1`` with n the
+    value of ``t_len`` at launch, ``d_nout = 0``, and the record
+    ``{m, drafts[:k], -1...}`` goes to ``rec[nrec % len(rec)]`` (int32
+    [R, SPEC_REC_WORDS]; ``nrec += 1``).  ``scratch`` (int64
+    [SPEC_SCRATCH_WORDS]) is zeroed once by the caller and re-armed by every
+    launch.  ``blocks``: blocks per row, 0 = the measured default.  The
+    caller guarantees KV room for n + k + 1 and ring room for k + 1 more
+    tokens.  Raises ValueError ahead of any launch on a bad argument."""
+    if not isinstance(logits, torch.Tensor) \
+            or logits.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("logits must be an fp32 or bf16 tensor")
+    if not logits.is_cuda:
+        raise ValueError("spec_verify runs on the GPU; got CPU tensors")
+    if logits.dim() != 2 or not logits.is_contiguous() \
+            or logits.shape[1] < 1:
+        raise ValueError("logits must be contiguous [k+1, V >= 1]")
+    k = int(k)
+    if not 1 <= k <= SPEC_MAX_K:
+        raise ValueError(f"k must be within 1..{SPEC_MAX_K}, got {k}")
+    rows, V = logits.shape
+    if rows != k + 1:
+        raise ValueError(f"logits must have k+1 = {k + 1} rows, got {rows}")
+    dev = logits.device
+    _spec_i32("drafts", drafts, k, dev)
+    for name, t in (("t_len", t_len), ("t_next", t_next), ("t_nout", t_nout),
+                    ("d_len", d_len), ("d_next", d_next), ("d_nout", d_nout),
+                    ("nrec", nrec), ("t_ring", t_ring)):
+        _spec_i32(name, t, 1, dev)
+    if t_ring.dim() != 1:
+        raise ValueError("t_ring must be one-dimensional")
+    if not isinstance(scratch, torch.Tensor) or scratch.dtype != torch.int64 \
+            or not scratch.is_contiguous() \
+            or scratch.numel() < SPEC_SCRATCH_WORDS or scratch.device != dev:
+        raise ValueError(f"scratch must be contiguous int64 "
+                         f"[{SPEC_SCRATCH_WORDS}] on the logits' device")
+    _spec_i32("rec", rec, SPEC_REC_WORDS, dev)
+    if rec.dim() != 2 or rec.shape[1] != SPEC_REC_WORDS:
+        raise ValueError(f"rec must be int32 [R >= 1, {SPEC_REC_WORDS}]")
+    _check(lib().launch_spec_verify(
+        _ptr(logits), V, 1 if logits.dtype == torch.bfloat16 else 0, rows, k,
+        int(blocks), _ptr(drafts), _ptr(scratch), _ptr(t_len), _ptr(t_next),
+        _ptr(t_ring), _ptr(t_nout), t_ring.numel(), _ptr(d_len),
+        _ptr(d_next), _ptr(d_nout), _ptr(rec), _ptr(nrec), rec.shape[0],
+        _stream()), "spec_verify")
+
+
+def spec_stage(ids: torch.Tensor, t_next: torch.Tensor,
+               d_ring: torch.Tensor, k: int):
+    """ids[0] = t_next[0], ids[1..k] = d_ring[0..k-1] (all int32, one
+    device), on the stream: the ids of a verify pass without a host read.
+    ``k`` = 0 stages the pending token alone."""
+    k = int(k)
+    if not 0 <= k <= SPEC_MAX_K:
+        raise ValueError(f"k must be within 0..{SPEC_MAX_K}, got {k}")
+    if not isinstance(ids, torch.Tensor) or not ids.is_cuda:
+        raise ValueError("spec_stage runs on the GPU; got CPU tensors")
+    _spec_i32("ids", ids, k + 1, ids.device)
+    _spec_i32("t_next", t_next, 1, ids.device)
+    _spec_i32("d_ring", d_ring, max(k, 1), ids.device)
+    _check(lib().launch_spec_stage(_ptr(ids), _ptr(t_next), _ptr(d_ring), k,
+                                   _stream()), "spec_stage")
 
 
 def gemm(X: torch.Tensor, W: torch.Tensor, Y: torch.Tensor,

@@ -32,6 +32,16 @@ MFMA prefill GEMMs (``forward_positions``), so verifying k tokens
 streams the weights ONCE instead of k times — the same
 bandwidth argument that makes batched decode pay.
 
+Device-side greedy path: with two single-GPU ``GPUModel`` engines (both
+advertise ``device_speculative``), plain greedy params and
+``k <= SPEC_MAX_K`` the whole loop runs on the GPU
+(``GPUModel.speculative_tokens``): the draft replays its decode graph, the
+verify pass keeps its logits on the device and ``k_spec_verify`` commits
+the accepted prefix into both engines' state; the host reads ids and one
+small record per cycle, once per chunk of cycles.  Everything else —
+stochastic params, ``logit_bias``, TP > 1, MoE, the NumPy engine — takes
+the host loop below (``device=`` of ``generate_speculative``).
+
 The reference has no speculative decoding (SURVEY §2 — single-model
 greedy/min-p only); this is a beyond-parity capability (ROADMAP §5).
 """
@@ -104,11 +114,63 @@ def _rewind(model, cache, n: int) -> None:
     cache.seq_len = n
 
 
+def _spec_max_k() -> int:
+    """``hip_ops.SPEC_MAX_K`` (most drafts per device verify pass); the
+    import is deferred so the host loop needs no torch."""
+    from ..ops.hip_ops import SPEC_MAX_K
+    return SPEC_MAX_K
+
+
+def device_path_block(draft, target, params: SamplingParams,
+                      k: int) -> Optional[str]:
+    """Why the device-side path does not apply to this call, or None when
+    it does: both engines advertise ``device_speculative``, plain greedy
+    params, no ``logit_bias``, ``k`` within ``SPEC_MAX_K``."""
+    for name, model in (("target", target), ("draft", draft)):
+        if not getattr(model, "device_speculative", False):
+            return f"the {name} engine has no device-side speculative path"
+    if params.strategy != "greedy":
+        return f"strategy {params.strategy!r} is not greedy"
+    if params.logit_bias:
+        return "logit_bias is applied on the host"
+    if k > _spec_max_k():
+        return f"k {k} exceeds SPEC_MAX_K {_spec_max_k()}"
+    return None
+
+
+def _generate_device(prompt, tokenizer, draft, target, max_tokens, k,
+                     stop_on_eos, on_token) -> GenerateResult:
+    """The device-side greedy path: ``target.speculative_tokens`` runs
+    draft steps, verify pass and commit on the GPU in chunks of cycles;
+    the host sees ids and per-cycle records only."""
+    prompt_ids = [int(t) for t in tokenizer.encode(prompt)]
+    eos = getattr(target.config, "eos_token_id", None)
+    t0 = time.perf_counter()
+    on_ids = None
+    if on_token is not None:
+        def on_ids(new_ids):
+            on_token(tokenizer.decode([int(t) for t in new_ids]))
+    out, recs = target.speculative_tokens(
+        draft, prompt_ids, max_tokens, k=k,
+        eos_id=eos if stop_on_eos else None, on_ids=on_ids)
+    total = time.perf_counter() - t0
+    out = [int(t) for t in out]
+    t_prefill = float(getattr(target, "last_prefill_time_s", 0.0))
+    res = GenerateResult(text=tokenizer.decode(out), token_ids=out,
+                         prefill_time_s=t_prefill,
+                         decode_time_s=max(total - t_prefill, 0.0))
+    res.spec_stats = {"proposed": sum(int(r[0]) for r in recs),
+                      "accepted": sum(int(r[1]) for r in recs),
+                      "verify_passes": len(recs)}
+    return res
+
+
 def generate_speculative(prompt: str, tokenizer, draft, target,
                          max_tokens: int = 200, k: int = 4,
                          stop_on_eos: bool = True,
                          params: Optional[SamplingParams] = None,
-                         on_token=None) -> GenerateResult:
+                         on_token=None,
+                         device: Optional[bool] = None) -> GenerateResult:
     """Decode ``target`` accelerated by ``draft`` proposals.
 
     ``params=None`` (or strategy "greedy") reproduces target-only
@@ -120,6 +182,13 @@ def generate_speculative(prompt: str, tokenizer, draft, target,
     speculative-decoding requirement).  Returns a GenerateResult; the
     extra attribute ``spec_stats`` holds ``{proposed, accepted,
     verify_passes}`` (acceptance rate = accepted / proposed).
+
+    ``device``: None routes a greedy call without ``logit_bias`` and with
+    ``k <= SPEC_MAX_K`` to the device-side path when both engines
+    advertise ``device_speculative`` (draft loop, verify and commit on the
+    GPU; ``on_token`` then fires once per chunk of cycles); False forces
+    the host loop below; True raises ValueError where the device path does
+    not apply.
     """
     if k < 1:
         raise ValueError("k must be >= 1")
@@ -132,6 +201,14 @@ def generate_speculative(prompt: str, tokenizer, draft, target,
         raise ValueError(
             "repetition/frequency/presence penalties are not supported "
             "under speculative decoding")
+    if device is None or device:
+        why = device_path_block(draft, target, params, k)
+        if why is None:
+            return _generate_device(prompt, tokenizer, draft, target,
+                                    max_tokens, k, stop_on_eos, on_token)
+        if device:
+            raise ValueError(f"device-side speculative decoding does not "
+                             f"apply: {why}")
     rng = np.random.default_rng(params.seed)
 
     def _pick(logits_row: np.ndarray) -> int:
