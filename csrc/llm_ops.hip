@@ -1895,38 +1895,42 @@ k_attn_t(const u16* __restrict__ q, const void* __restrict__ kc,
 // by the LAST-arriving block of each head via the agent-scope
 // release/acquire + ticket recipe (guide §6 G16) — placement-independent
 // and graph-replay-safe (the merger resets its head's counter).
+// For SPLIT 2..4 the in-block form (k_attn_dec_blk_t) puts the SPLIT
+// chunks into ONE block of 256 * SPLIT threads and merges through LDS:
+// same chunk and merge source, same bits, no global hand-off.
 // The SPLIT-1 chunk also handles the current token from registers and
 // one block per kv-head persists the new k/v to the pool.
 // Gemma-2 semantics included: sliding window + attn-logit softcap.
 // ====================================================================
 
-// The attention block's body, shared by the plain and the prefetching
-// kernel: `chunk` of `SPLIT` for head blockIdx.x of row blockIdx.z.
+// One chunk of one head, by the four waves `wave` = 0..3 that share the
+// LDS region `red` ([4][hd] + [4][2] floats): `chunk` of `SPLIT` for head
+// blockIdx.x of row blockIdx.z.  Wave 0 leaves the chunk's partial —
+// m, l, then the hd UNnormalized accumulators — in slot `pidx` of `parts`
+// ([.][hd + 2] floats: global scratch in the ticket kernels, LDS in the
+// in-block ones), or with SPLIT == 1 writes the normalized row to `out`.
+// Holds one __syncthreads(): every thread of the block calls it.
 template <bool KV8>
-DEVINL void attn_dec_body(char* smem, const int chunk, const int SPLIT,
-                          const u16* __restrict__ qkv, void* __restrict__ kc,
-                          void* __restrict__ vc, u16* __restrict__ out,
-                          const int* __restrict__ len_ptr,
-                          const float* __restrict__ cost,
-                          const float* __restrict__ sint,
-                          float* __restrict__ kS, float* __restrict__ vS,
-                          float* __restrict__ scratch, int* __restrict__ cnt,
-                          int nh, int kvh, int hd, int S, float scale,
-                          float softcap, int window) {
-  float* red = (float*)smem;              // [4][hd] + [4][2] + flag
-  int* lastflag = (int*)(red + 4 * hd + 8);
-
+DEVINL void attn_dec_chunk(float* red, const int chunk, const int SPLIT,
+                           const int wave, const int lane,
+                           float* __restrict__ parts, const int pidx,
+                           const u16* __restrict__ qkv, void* __restrict__ kc,
+                           void* __restrict__ vc, u16* __restrict__ out,
+                           const int* __restrict__ len_ptr,
+                           const float* __restrict__ cost,
+                           const float* __restrict__ sint,
+                           float* __restrict__ kS, float* __restrict__ vS,
+                           int nh, int kvh, int hd, int S, float scale,
+                           float softcap, int window) {
   const int h = blockIdx.x;
-  // batch axis (lockstep sequences): per-b qkv/out rows, KV pool,
-  // scales, merge scratch and tickets; the position is shared
+  // batch axis (lockstep sequences): per-b qkv/out rows, KV pool and
+  // scales; the position is shared
   const int b = blockIdx.z;
   qkv += (size_t)b * (nh + 2 * kvh) * hd;
   out += (size_t)b * nh * hd;
   kc = (char*)kc + (size_t)b * kvh * S * hd * (KV8 ? 1 : 2);
   vc = (char*)vc + (size_t)b * kvh * S * hd * (KV8 ? 1 : 2);
   if (KV8) { kS += (size_t)b * kvh * S; vS += (size_t)b * kvh * S; }
-  scratch += (size_t)b * nh * SPLIT * (hd + 2);
-  cnt += b * nh;
   const int grp = nh / kvh;
   const int kvhead = h / grp;
   // RAGGED batch: each sequence row sits at its own position
@@ -1944,7 +1948,6 @@ DEVINL void attn_dec_body(char* smem, const int chunk, const int SPLIT,
 
   const int LP = hd / 8;
   const int PP = 64 / LP;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int p = lane / LP, d0 = (lane % LP) * 8;
   const int hd2 = hd / 2;
   const float* cp = cost + (size_t)pos * hd2;
@@ -2171,7 +2174,7 @@ DEVINL void attn_dec_body(char* smem, const int chunk, const int SPLIT,
   }
   __syncthreads();
 
-  float* part = scratch + ((size_t)h * SPLIT + chunk) * (hd + 2);
+  float* part = parts + (size_t)pidx * (hd + 2);
   if (wave == 0) {
     float mt = fmaxf(fmaxf(mls[0], mls[2]), fmaxf(mls[4], mls[6]));
     float lt = 0.f, sc[4];
@@ -2199,6 +2202,60 @@ DEVINL void attn_dec_body(char* smem, const int chunk, const int SPLIT,
       if (lane == 0) { part[0] = mt; part[1] = lt; }
     }
   }
+}
+
+// One wave merges a head's SPLIT chunk partials at `base`
+// ([SPLIT][hd + 2] floats, as attn_dec_chunk leaves them) into the
+// normalized row `out_h`: max over the chunks, then sums for
+// c = 0..SPLIT-1 — the order does not depend on who calls it.
+DEVINL void attn_dec_merge(const float* base, const int SPLIT, const int lane,
+                           const int hd, u16* out_h) {
+  float mt = -INFINITY;
+  for (int c = 0; c < SPLIT; c++)
+    mt = fmaxf(mt, base[(size_t)c * (hd + 2)]);
+  float lt = 0.f;
+  for (int c = 0; c < SPLIT; c++) {
+    float mc = base[(size_t)c * (hd + 2)];
+    if (mc != -INFINITY)
+      lt += base[(size_t)c * (hd + 2) + 1] * __expf(mc - mt);
+  }
+  float inv = 1.f / lt;
+  for (int d = lane; d < hd; d += 64) {
+    float v = 0.f;
+    for (int c = 0; c < SPLIT; c++) {
+      float mc = base[(size_t)c * (hd + 2)];
+      if (mc != -INFINITY)
+        v += base[(size_t)c * (hd + 2) + 2 + d] * __expf(mc - mt);
+    }
+    out_h[d] = f2b(v * inv);
+  }
+}
+
+// The ticket form's attention block (256 threads), shared by the plain
+// and the prefetching kernel: `chunk` of `SPLIT` for head blockIdx.x of
+// row blockIdx.z; partials cross blocks through `scratch`, tickets in
+// `cnt` (both per batch row).
+template <bool KV8>
+DEVINL void attn_dec_body(char* smem, const int chunk, const int SPLIT,
+                          const u16* __restrict__ qkv, void* __restrict__ kc,
+                          void* __restrict__ vc, u16* __restrict__ out,
+                          const int* __restrict__ len_ptr,
+                          const float* __restrict__ cost,
+                          const float* __restrict__ sint,
+                          float* __restrict__ kS, float* __restrict__ vS,
+                          float* __restrict__ scratch, int* __restrict__ cnt,
+                          int nh, int kvh, int hd, int S, float scale,
+                          float softcap, int window) {
+  float* red = (float*)smem;              // [4][hd] + [4][2] + flag
+  int* lastflag = (int*)(red + 4 * hd + 8);
+  const int h = blockIdx.x;
+  const int b = blockIdx.z;
+  scratch += (size_t)b * nh * SPLIT * (hd + 2);
+  cnt += b * nh;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  attn_dec_chunk<KV8>(red, chunk, SPLIT, wave, lane, scratch,
+                      h * SPLIT + chunk, qkv, kc, vc, out, len_ptr, cost,
+                      sint, kS, vS, nh, kvh, hd, S, scale, softcap, window);
   if (SPLIT == 1) return;
 
   // publish + ticket (G16 R1: plain stores -> per-wave drain -> barrier
@@ -2219,30 +2276,39 @@ DEVINL void attn_dec_body(char* smem, const int chunk, const int SPLIT,
   if (threadIdx.x == 0)
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
   __syncthreads();
-  if (wave == 0) {
-    const float* base = scratch + (size_t)h * SPLIT * (hd + 2);
-    float mt = -INFINITY;
-    for (int c = 0; c < SPLIT; c++)
-      mt = fmaxf(mt, base[(size_t)c * (hd + 2)]);
-    float lt = 0.f;
-    for (int c = 0; c < SPLIT; c++) {
-      float mc = base[(size_t)c * (hd + 2)];
-      if (mc != -INFINITY)
-        lt += base[(size_t)c * (hd + 2) + 1] * __expf(mc - mt);
-    }
-    float inv = 1.f / lt;
-    for (int d = lane; d < hd; d += 64) {
-      float v = 0.f;
-      for (int c = 0; c < SPLIT; c++) {
-        float mc = base[(size_t)c * (hd + 2)];
-        if (mc != -INFINITY)
-          v += base[(size_t)c * (hd + 2) + 2 + d] * __expf(mc - mt);
-      }
-      out[(size_t)h * hd + d] = f2b(v * inv);
-    }
-  }
+  if (wave == 0)
+    attn_dec_merge(scratch + (size_t)h * SPLIT * (hd + 2), SPLIT, lane, hd,
+                   out + ((size_t)b * nh + h) * hd);
   __syncthreads();
   if (threadIdx.x == 0) cnt[h] = 0;  // re-arm for the next graph replay
+}
+
+// The in-block form: ONE block of 256 * SPLIT threads per (head, row).
+// Waves 4c..4c+3 are chunk c's four waves and do what a ticket block
+// does, on their own `red` region; the chunk partials stay in LDS and
+// wave 0 merges them after one barrier.  No global scratch, no fence, no
+// atomic, no ticket: the kernel takes neither `scratch` nor `cnt`.
+template <bool KV8, int SPLIT>
+DEVINL void attn_dec_body_blk(char* smem, const u16* __restrict__ qkv,
+                              void* __restrict__ kc, void* __restrict__ vc,
+                              u16* __restrict__ out,
+                              const int* __restrict__ len_ptr,
+                              const float* __restrict__ cost,
+                              const float* __restrict__ sint,
+                              float* __restrict__ kS, float* __restrict__ vS,
+                              int nh, int kvh, int hd, int S, float scale,
+                              float softcap, int window) {
+  const int wg = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int chunk = wg >> 2;
+  float* red = (float*)smem + chunk * (4 * hd + 8);  // [SPLIT] regions
+  float* parts = (float*)smem + SPLIT * (4 * hd + 8);  // [SPLIT][hd + 2]
+  attn_dec_chunk<KV8>(red, chunk, SPLIT, wg & 3, lane, parts, chunk,
+                      qkv, kc, vc, out, len_ptr, cost, sint, kS, vS, nh, kvh,
+                      hd, S, scale, softcap, window);
+  __syncthreads();
+  if (wg == 0)
+    attn_dec_merge(parts, SPLIT, lane, hd,
+                   out + ((size_t)blockIdx.z * nh + blockIdx.x) * hd);
 }
 
 // --------------------------------------------------------------------
@@ -2290,12 +2356,15 @@ DEVINL uint32_t attn_pf_trip(const u4v* __restrict__ base, long nseg, F seg) {
   return a;
 }
 
-DEVINL void attn_dec_prefetch(const AttnPf& pf, const int split) {
+// `arows`: the grid.y rows ahead of the prefetch rows (the attention
+// blocks: `split` in the ticket form, 1 in the in-block form).  Threads
+// 0..255 of the block work.
+DEVINL void attn_dec_prefetch(const AttnPf& pf, const int arows) {
   const uint32_t nx = gridDim.x;
-  const uint32_t pfy = gridDim.y - split;
+  const uint32_t pfy = gridDim.y - arows;
   const uint32_t npb = nx * pfy * gridDim.z;  // prefetch blocks in all
   const uint32_t pb =
-      (blockIdx.z * pfy + (blockIdx.y - split)) * nx + blockIdx.x;
+      (blockIdx.z * pfy + (blockIdx.y - arows)) * nx + blockIdx.x;
   uint32_t acc = 0;
   // The regions form one range, concatenated in whole trips and dealt
   // to the blocks round-robin: `g0` = trips handed out so far, mod npb.
@@ -2374,10 +2443,42 @@ k_attn_dec_t(const u16* __restrict__ qkv, void* __restrict__ kc,
                      softcap, window);
 }
 
+// In-block form: grid (nh, 1 + PFY, batch), 256 * SPLIT threads; row
+// y == 0 is the attention block, rows y >= 1 are prefetch blocks in which
+// threads 0..255 work and the rest leave at once (the prefetch geometry
+// stays nh x 256 threads per row).  No scratch / cnt arguments.
+template <bool KV8, int SPLIT, bool PF, typename... PFA>
+__global__ void __launch_bounds__(256 * SPLIT)
+k_attn_dec_blk_t(const u16* __restrict__ qkv, void* __restrict__ kc,
+                 void* __restrict__ vc, u16* __restrict__ out,
+                 const int* __restrict__ len_ptr,
+                 const float* __restrict__ cost,
+                 const float* __restrict__ sint, float* __restrict__ kS,
+                 float* __restrict__ vS, int nh, int kvh, int hd, int S,
+                 float scale, float softcap, int window, PFA... pfa) {
+  static_assert(sizeof...(PFA) == (PF ? 1 : 0), "PF takes one AttnPf");
+  static_assert(SPLIT >= 2 && SPLIT <= 4, "256 * SPLIT threads, one block");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  if constexpr (PF) {
+    if (blockIdx.y >= 1) {
+      if (threadIdx.x >= 256) return;
+      const AttnPf& pf = (pfa, ...);
+      attn_dec_prefetch(pf, 1);
+      return;
+    }
+  }
+  attn_dec_body_blk<KV8, SPLIT>(smem, qkv, kc, vc, out, len_ptr, cost, sint,
+                                kS, vS, nh, kvh, hd, S, scale, softcap,
+                                window);
+}
+
 // Launches the attention kernel with `pf_blocks` prefetch blocks (rounded
 // to whole grid.y rows of nh blocks) over up to four regions; stride0 is
 // "rows per consumer block x row bytes" of region 0's consumer, 0 to walk
 // it flat.  pf_blocks == 0 dispatches the plain kernel.
+// merge: 0 = in-block form when 2 <= split <= 4, else the ticket form;
+// 1 = ticket form; 2 = in-block form (an error where 256 * split threads
+// exceed a block).  split == 1 is one chunk either way: the ticket kernel.
 static hipError_t attn_dec_launch(const void* qkv, void* kc, void* vc,
                                   void* out, const void* len_ptr,
                                   const void* cost, const void* sint,
@@ -2385,9 +2486,43 @@ static hipError_t attn_dec_launch(const void* qkv, void* kc, void* vc,
                                   void* cnt, int split, int batch, int nh,
                                   int kvh, int hd, int S, float scale,
                                   float softcap, int window, int pf_blocks,
-                                  const AttnPf& pf, hipStream_t stream) {
+                                  const AttnPf& pf, int merge,
+                                  hipStream_t stream) {
+  if (merge < 0 || merge > 2 || split < 1) return hipErrorInvalidValue;
+  if (merge == 2 && 256 * split > 1024) return hipErrorInvalidValue;
   size_t lds = (4 * hd + 8) * sizeof(float) + 16;
   const int pfy = pf_blocks > 0 ? (pf_blocks + nh - 1) / nh : 0;
+  if (merge != 1 && split >= 2 && split <= 4) {
+    const size_t blds =
+        (size_t)split * ((4 * hd + 8) + (hd + 2)) * sizeof(float);
+#define ATTN_BLK_ARGS                                                        \
+  (const u16*)qkv, kc, vc, (u16*)out, (const int*)len_ptr,                   \
+      (const float*)cost, (const float*)sint, (float*)kS, (float*)vS, nh,    \
+      kvh, hd, S, scale, softcap, window
+#define ATTN_BLK_CASE(KV8V, SP)                                              \
+  do {                                                                       \
+    if (pfy > 0)                                                             \
+      hipLaunchKernelGGL((k_attn_dec_blk_t<KV8V, SP, true, AttnPf>),         \
+                         dim3(nh, 1 + pfy, batch), dim3(256 * SP), blds,     \
+                         stream, ATTN_BLK_ARGS, pf);                         \
+    else                                                                     \
+      hipLaunchKernelGGL((k_attn_dec_blk_t<KV8V, SP, false>),                \
+                         dim3(nh, 1, batch), dim3(256 * SP), blds, stream,   \
+                         ATTN_BLK_ARGS);                                     \
+  } while (0)
+#define ATTN_BLK_SPLIT(KV8V)                                                 \
+  do {                                                                       \
+    if (split == 2) ATTN_BLK_CASE(KV8V, 2);                                  \
+    else if (split == 3) ATTN_BLK_CASE(KV8V, 3);                             \
+    else ATTN_BLK_CASE(KV8V, 4);                                             \
+  } while (0)
+    if (kv8) ATTN_BLK_SPLIT(true);
+    else ATTN_BLK_SPLIT(false);
+#undef ATTN_BLK_SPLIT
+#undef ATTN_BLK_CASE
+#undef ATTN_BLK_ARGS
+    return hipGetLastError();
+  }
 #define ATTN_DEC_ARGS                                                        \
   (const u16*)qkv, kc, vc, (u16*)out, (const int*)len_ptr,                   \
       (const float*)cost, (const float*)sint, (float*)kS, (float*)vS,        \
@@ -2418,13 +2553,13 @@ extern "C" hipError_t launch_attn_dec_pf(
     void* scratch, void* cnt, int split, int batch, int nh, int kvh, int hd,
     int S, float scale, float softcap, int window, int pf_blocks,
     const void* p0, long n0, const void* p1, long n1, const void* p2,
-    long n2, const void* p3, long n3, long stride0, void* sink,
+    long n2, const void* p3, long n3, long stride0, void* sink, int merge,
     hipStream_t stream) {
   AttnPf pf{{p0, p1, p2, p3}, {n0, n1, n2, n3}, stride0, (float*)sink, -1};
   if (pf_blocks > 0 && sink == nullptr) return hipErrorInvalidValue;
   return attn_dec_launch(qkv, kc, vc, out, len_ptr, cost, sint, kS, vS, kv8,
                          scratch, cnt, split, batch, nh, kvh, hd, S, scale,
-                         softcap, window, pf_blocks, pf, stream);
+                         softcap, window, pf_blocks, pf, merge, stream);
 }
 
 extern "C" hipError_t launch_attn_dec(const void* qkv, void* kc, void* vc,
@@ -2435,10 +2570,10 @@ extern "C" hipError_t launch_attn_dec(const void* qkv, void* kc, void* vc,
                                       int batch,
                                       int nh, int kvh, int hd, int S,
                                       float scale, float softcap, int window,
-                                      hipStream_t stream) {
+                                      int merge, hipStream_t stream) {
   return attn_dec_launch(qkv, kc, vc, out, len_ptr, cost, sint, kS, vS, kv8,
                          scratch, cnt, split, batch, nh, kvh, hd, S, scale,
-                         softcap, window, 0, AttnPf{}, stream);
+                         softcap, window, 0, AttnPf{}, merge, stream);
 }
 
 // ====================================================================
@@ -2754,6 +2889,43 @@ DEVINL int unpack_idx(uint64_t p) { return 0x7fffffff - (int)(uint32_t)p; }
 // pass 1 (min-p only): global max logit -> gmax[b] (packed).
 // Batched: grid.y = sequence row b (lbf16: logits stored bf16 — the
 // batched lm_head GEMM path emits bf16 rows).
+// Grid-wide visit of one logits row: f(i, value) once per element.  Whole
+// 16-B vectors (4 fp32 / 8 bf16) go grid-stride, the tail behind the last
+// whole vector scalar; a row whose base is not 16-B aligned (rows of a
+// batch with V off the vector size) is scalar throughout.  What f does
+// with an element depends on its index and value alone, so the visiting
+// order is free.
+template <typename F>
+DEVINL void logits_scan(const float* __restrict__ lf,
+                        const u16* __restrict__ lh, int V, int lbf16, F f) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  const int nt = gridDim.x * 256;
+  int done = 0;
+  if (lbf16) {
+    if (((uintptr_t)lh & 15) == 0) {
+      const int nv = V >> 3;
+      for (int k = t; k < nv; k += nt) {
+        s8v x = ((const s8v*)lh)[k];
+#pragma unroll
+        for (int j = 0; j < 8; j++) f(k * 8 + j, b2f(((u16*)&x)[j]));
+      }
+      done = nv << 3;
+    }
+    for (int i = done + t; i < V; i += nt) f(i, b2f(lh[i]));
+  } else {
+    if (((uintptr_t)lf & 15) == 0) {
+      const int nv = V >> 2;
+      for (int k = t; k < nv; k += nt) {
+        f4v x = ((const f4v*)lf)[k];
+#pragma unroll
+        for (int j = 0; j < 4; j++) f(k * 4 + j, x[j]);
+      }
+      done = nv << 2;
+    }
+    for (int i = done + t; i < V; i += nt) f(i, lf[i]);
+  }
+}
+
 DEVINL void logit_max_body(const void* __restrict__ logits, int V, int lbf16,
                            unsigned long long* __restrict__ gmax) {
   const int b = blockIdx.y;
@@ -2762,10 +2934,9 @@ DEVINL void logit_max_body(const void* __restrict__ logits, int V, int lbf16,
   const u16* lh = (const u16*)logits + (size_t)b * V;
   float mv = -INFINITY;
   int mi = 0;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < V; i += gridDim.x * 256) {
-    float v = lbf16 ? b2f(lh[i]) : lf[i];
+  logits_scan(lf, lh, V, lbf16, [&](int i, float v) {
     if (v > mv || (v == mv && i < mi)) { mv = v; mi = i; }
-  }
+  });
   uint64_t pk = pack_ki(fkey(mv), mi);
 #pragma unroll
   for (int w = 1; w < 64; w <<= 1) {
@@ -2916,9 +3087,8 @@ DEVINL void sample_pick_body(
   const uint32_t c = (uint32_t)(*ctr) ^ ((uint32_t)b * 0x85ebca6bu);
   float bv = -INFINITY;
   int bi = 0x7fffffff;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < V; i += gridDim.x * 256) {
-    float v = lbf16 ? b2f(lh[i]) : lf[i];
-    if (SEL ? (fkey(v) < tau) : (v < thresh)) continue;
+  logits_scan(lf, lh, V, lbf16, [&](int i, float v) {
+    if (SEL ? (fkey(v) < tau) : (v < thresh)) return;
     float sc = v;
     if (!greedy) {
       uint32_t r = hash32(hash32((uint32_t)i ^ (c * 0x9e3779b9u)) ^
@@ -2927,7 +3097,7 @@ DEVINL void sample_pick_body(
       sc = v * inv_temp - __logf(-__logf(u));
     }
     if (sc > bv || (sc == bv && i < bi)) { bv = sc; bi = i; }
-  }
+  });
   sample_pick_commit(bv, bi, V, gmax, pick, cnt, next_token, out_ring, nout,
                      len_ptr, bump_len, SEL ? sel : nullptr);
 }
@@ -3020,9 +3190,8 @@ k_sample_pick_rows(const void* __restrict__ logits, int V, int lbf16,
   const uint32_t k1 = hash32(k0 ^ samp[SAMP_SEED + 1] ^ 0x85ebca6bu);
   float bv = -INFINITY;
   int bi = 0x7fffffff;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < V; i += gridDim.x * 256) {
-    float v = lbf16 ? b2f(lh[i]) : lf[i];
-    if (selected ? (fkey(v) < tau) : (v < thresh)) continue;
+  logits_scan(lf, lh, V, lbf16, [&](int i, float v) {
+    if (selected ? (fkey(v) < tau) : (v < thresh)) return;
     float sc = v;
     if (!greedy) {
       uint32_t r = hash32(hash32((uint32_t)i ^ k0) ^ k1);
@@ -3030,7 +3199,7 @@ k_sample_pick_rows(const void* __restrict__ logits, int V, int lbf16,
       sc = v * inv_temp - __logf(-__logf(u));
     }
     if (sc > bv || (sc == bv && i < bi)) { bv = sc; bi = i; }
-  }
+  });
   sample_pick_commit(bv, bi, V, gmax, pick, cnt, next_token, out_ring, nout,
                      len_ptr, bump_len, selected ? sel : nullptr);
 }
@@ -3213,22 +3382,41 @@ k_sample_select_rows2(const void* __restrict__ logits, int V, int lbf16,
                            gmax, sel);
 }
 
+// Blocks per row of the launches whose blocks end in atomics on one word
+// per row (k_logit_max*: atomicMax; k_sample_pick*: atomicMax + returning
+// ticket).  Those serialize at 11-13 ns each, so the block count is the
+// kernel's duration once it is in the hundreds: one block per
+// SAMPLE_PICK_SPAN elements (one 16-B fp32 load per thread), at most
+// SAMPLE_PICK_CAP (profiles/attn_inblock_merge.md has the sweep).
+// `blocks` > 0 overrides.  Any count gives the same winner: it is defined
+// over element indices.
+constexpr int SAMPLE_PICK_SPAN = 1024;
+constexpr int SAMPLE_PICK_CAP = 64;
+static int sample_pick_blocks(int V, int batch, int blocks) {
+  if (blocks > 0) return blocks;
+  blocks = (V + SAMPLE_PICK_SPAN - 1) / SAMPLE_PICK_SPAN;
+  if (blocks > SAMPLE_PICK_CAP) blocks = SAMPLE_PICK_CAP;
+  // batched rows: keep TOTAL thread count constant (the B=8 sampler
+  // measured 102 us with a full grid per row, and 10 us at 16 blocks
+  // per row against 15 at 64)
+  if (batch > 1) {
+    const int floor_ = blocks < 16 ? blocks : 16;
+    blocks = blocks / batch + 1;
+    if (blocks < floor_) blocks = floor_;
+  }
+  return blocks < 1 ? 1 : blocks;
+}
+
 extern "C" hipError_t launch_sample(const void* logits, int V, int lbf16,
                                     int batch, long ring_stride, float min_p,
                                     int greedy, uint64_t seed, float inv_temp,
                                     void* ctr, void* gmax, void* pick,
                                     void* cnt, void* next_token,
                                     void* out_ring, void* nout,
-                                    void* len_ptr, int bump_len,
+                                    void* len_ptr, int bump_len, int blocks,
                                     hipStream_t stream) {
-  int blocks = (V + 255) / 256;
-  if (blocks > 512) blocks = 512;
-  // batched rows: keep TOTAL thread count constant (the B=8 sampler
-  // measured 102 us with a full grid per row)
-  if (batch > 1) {
-    blocks = blocks / batch + 1;
-    if (blocks < 16) blocks = 16;
-  }
+  if (blocks < 0 || blocks > 65535) return hipErrorInvalidValue;
+  blocks = sample_pick_blocks(V, batch, blocks);
   if (!greedy)
     hipLaunchKernelGGL(k_logit_max, dim3(blocks, batch), dim3(256), 0,
                        stream, logits, V, lbf16, (unsigned long long*)gmax,
@@ -3256,14 +3444,9 @@ extern "C" hipError_t launch_sample_sel(
   if (greedy || (top_k <= 0 && !(top_p < 1.0f)))
     return launch_sample(logits, V, lbf16, batch, ring_stride, min_p, greedy,
                          seed, inv_temp, ctr, gmax, pick, cnt, next_token,
-                         out_ring, nout, len_ptr, bump_len, stream);
+                         out_ring, nout, len_ptr, bump_len, 0, stream);
   if (top_k > V) top_k = V;
-  int blocks = (V + 255) / 256;
-  if (blocks > 512) blocks = 512;
-  if (batch > 1) {
-    blocks = blocks / batch + 1;
-    if (blocks < 16) blocks = 16;
-  }
+  const int blocks = sample_pick_blocks(V, batch, 0);
   // few blocks per row: every block merges its bins into the same handful
   // of hot histogram words, so the merge cost grows with the block count
   int sblocks = (V + 2047) / 2048;
@@ -3306,12 +3489,7 @@ extern "C" hipError_t launch_sample_rows(
     void* samp, int any_sampled, int any_select, int chain, void* gmax,
     void* pick, void* cnt, void* next_token, void* out_ring, void* nout,
     void* len_ptr, int bump_len, void* sel, hipStream_t stream) {
-  int blocks = (V + 255) / 256;
-  if (blocks > 512) blocks = 512;
-  if (batch > 1) {
-    blocks = blocks / batch + 1;
-    if (blocks < 16) blocks = 16;
-  }
+  const int blocks = sample_pick_blocks(V, batch, 0);
   if (!any_sampled && !any_select) {
     // greedy reads neither seed nor counter value; `samp` only stands in
     // as a readable 8-byte word for the kernel's counter load
@@ -3529,7 +3707,7 @@ extern "C" hipError_t launch_tokstat_mark(void* stat_row, const void* ids,
 }
 
 // grid: one thread per 16 B group of a row (4 fp32 / 8 bf16 elements),
-// capped like launch_sample's; the loops are grid-stride, so the scalar
+// capped at 512 blocks; the loops are grid-stride, so the scalar
 // fallback of a misaligned row is covered by the same grid
 extern "C" hipError_t launch_logit_adjust(void* logits, int V, int lbf16,
                                           int batch, void* stat,

@@ -520,6 +520,13 @@ class GPUModel:
         # T~4k split8 1108 > split16 1050; T~8k split16 963 > split32
         self.attn_split = (int(_sp) if _sp else
                            min(16, max(2, self.max_seq // 512)))
+        # how a head's chunks combine (ho.attn_dec `merge`): same bits
+        # either way; "auto" is one block per head while split <= 4
+        self.attn_merge = _os.environ.get("LLM_ATTN_MERGE") or "auto"
+        if self.attn_merge not in ho.ATTN_MERGE:
+            raise ValueError(f"LLM_ATTN_MERGE must be one of "
+                             f"{sorted(ho.ATTN_MERGE)}, got "
+                             f"{self.attn_merge!r}")
         self.attn_scratch = torch.zeros(
             self.nh_l * self.attn_split * (hd + 2), dtype=torch.float32,
             device=dev)
@@ -705,7 +712,8 @@ class GPUModel:
                             self.nh_l, self.kvh_l, self.hd, self.scale,
                             softcap=self.attn_softcap, window=window or 0,
                             split=self.attn_split, kS=self.k_scale[i],
-                            vS=self.v_scale[i], batch=M)
+                            vS=self.v_scale[i], batch=M,
+                            merge=self.attn_merge)
             else:
                 self._linear(lw, "wq", xn, self.b_q, M=M)
                 self._linear(lw, "wk", xn, self.b_k, M=M)
@@ -1730,7 +1738,7 @@ class GPUModel:
                      self.attn_scratch, self.attn_cnt,
                      self.nh_l, self.kvh_l, self.hd, self.scale,
                      softcap=self.attn_softcap, window=window or 0,
-                     split=self.attn_split,
+                     split=self.attn_split, merge=self.attn_merge,
                      kS=self.k_scale[i], vS=self.v_scale[i], **pfkw)
             if self.gemma:
                 self._dgemv(lw, "wo", self.b_att[0], t1)
@@ -1924,7 +1932,7 @@ class GPUModel:
                         self.nh_l, self.kvh_l, self.hd, self.scale,
                         softcap=self.attn_softcap, window=window or 0,
                         split=self.attn_split, kS=self.k_scale[i],
-                        vS=self.v_scale[i], batch=B)
+                        vS=self.v_scale[i], batch=B, merge=self.attn_merge)
             if self.gemma:
                 proj(lw["wo_q"], lw["wo_s"], self.b_att, nhh, t1, nhh, H)
                 proj(lw["wgu_q"], lw["wgu_s"], t1, H, gu, H, 2 * I,

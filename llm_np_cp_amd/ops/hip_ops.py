@@ -49,13 +49,14 @@ _SIGS = {
     "launch_attn_dec": [ctypes.c_void_p] * 9 + [ctypes.c_int] +
                        [ctypes.c_void_p] * 2 + [ctypes.c_int] * 6 +
                        [ctypes.c_float, ctypes.c_float, ctypes.c_int,
-                        ctypes.c_void_p],
+                        ctypes.c_int, ctypes.c_void_p],
     "launch_attn_dec_pf": [ctypes.c_void_p] * 9 + [ctypes.c_int] +
                           [ctypes.c_void_p] * 2 + [ctypes.c_int] * 6 +
                           [ctypes.c_float, ctypes.c_float, ctypes.c_int,
                            ctypes.c_int] +
                           [ctypes.c_void_p, ctypes.c_long] * 4 +
-                          [ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p],
+                          [ctypes.c_long, ctypes.c_void_p, ctypes.c_int,
+                           ctypes.c_void_p],
     "launch_glu": [ctypes.c_void_p] * 3 + [ctypes.c_long, ctypes.c_int,
                                            ctypes.c_void_p],
     "launch_embed": [ctypes.c_void_p] * 3 + [ctypes.c_int] * 2 +
@@ -64,7 +65,7 @@ _SIGS = {
                       ctypes.c_int, ctypes.c_long, ctypes.c_float,
                       ctypes.c_int, ctypes.c_uint64, ctypes.c_float] +
                      [ctypes.c_void_p] * 8 +
-                     [ctypes.c_int, ctypes.c_void_p],
+                     [ctypes.c_int, ctypes.c_int, ctypes.c_void_p],
     "launch_sample_sel": [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                           ctypes.c_int, ctypes.c_long, ctypes.c_float,
                           ctypes.c_int, ctypes.c_uint64, ctypes.c_float] +
@@ -317,6 +318,16 @@ def attn_prefill_mfma(q: torch.Tensor, k_cache: torch.Tensor,
         window, _stream()), "attn_prefill_mfma")
 
 
+ATTN_MERGE = {"auto": 0, "ticket": 1, "block": 2}
+
+
+def _attn_merge(merge: str) -> int:
+    if merge not in ATTN_MERGE:
+        raise ValueError(f"merge must be one of {sorted(ATTN_MERGE)}, "
+                         f"got {merge!r}")
+    return ATTN_MERGE[merge]
+
+
 def attn_dec(qkv: torch.Tensor, k_cache: torch.Tensor,
              v_cache: torch.Tensor, out: torch.Tensor,
              len_ptr: torch.Tensor, cos_t: torch.Tensor,
@@ -324,12 +335,19 @@ def attn_dec(qkv: torch.Tensor, k_cache: torch.Tensor,
              cnt: torch.Tensor, nh: int, kvh: int, hd: int,
              scale: float, softcap: float = 0.0, window: int = 0,
              split: int = 1, kS: torch.Tensor | None = None,
-             vS: torch.Tensor | None = None, batch: int = 1):
+             vS: torch.Tensor | None = None, batch: int = 1, *,
+             merge: str = "auto"):
     """Fused decode attention: RoPE(q,k) + KV write + online softmax,
-    KV range split over `split` blocks/head (last-arriver merge).
+    KV range split into `split` chunks per head.
     kS/vS given => fp8 KV pool (quantized write + dequant scan).
     batch>1: grid.z = lockstep sequence rows (per-b qkv/out rows, KV
-    pools, scratch and tickets; shared device position)."""
+    pools, scratch and tickets; shared device position).
+    merge: how the chunks of a head combine.  "ticket": one 256-thread
+    block per chunk, partials through `scratch`, the last-arriving block
+    (ticket in `cnt`) merges.  "block": one block of 256 * split threads
+    per head, partials through LDS; `scratch` and `cnt` are not touched;
+    split <= 4 only.  "auto": "block" where 2 <= split <= 4.  The bits
+    are the same either way; split == 1 has nothing to merge."""
     S = k_cache.shape[-2]
     _check(lib().launch_attn_dec(
         _ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(out), _ptr(len_ptr),
@@ -337,7 +355,8 @@ def attn_dec(qkv: torch.Tensor, k_cache: torch.Tensor,
         1 if kS is not None else 0,
         _ptr(scratch), _ptr(cnt), split, batch,
         nh, kvh, hd, S, ctypes.c_float(scale),
-        ctypes.c_float(softcap), window, _stream()), "attn_dec")
+        ctypes.c_float(softcap), window, _attn_merge(merge), _stream()),
+        "attn_dec")
 
 
 def attn_dec_pf(qkv: torch.Tensor, k_cache: torch.Tensor,
@@ -349,9 +368,10 @@ def attn_dec_pf(qkv: torch.Tensor, k_cache: torch.Tensor,
                 split: int = 1, kS: torch.Tensor | None = None,
                 vS: torch.Tensor | None = None, batch: int = 1, *,
                 regions=(), pf_blocks: int = 0, stride0: int = 0,
-                sink: torch.Tensor | None = None):
+                sink: torch.Tensor | None = None, merge: str = "auto"):
     """`attn_dec` whose launch also carries `pf_blocks` prefetch blocks
-    (rounded up to whole grid rows of `nh`): they pull up to four
+    (rounded up to whole grid rows of `nh`; in the "block" merge form the
+    first 256 threads of each such block work): they pull up to four
     `regions`, (device address, bytes) pairs, into the cache hierarchy
     while the attention blocks wait on their latency chain, and write
     nothing.  `stride0`: bytes one consumer block reads of region 0 (L2
@@ -373,7 +393,7 @@ def attn_dec_pf(qkv: torch.Tensor, k_cache: torch.Tensor,
         _ptr(scratch), _ptr(cnt), split, batch,
         nh, kvh, hd, S, ctypes.c_float(scale),
         ctypes.c_float(softcap), window, pf_blocks, *flat, stride0,
-        _ptr(sink), _stream()), "attn_dec_pf")
+        _ptr(sink), _attn_merge(merge), _stream()), "attn_dec_pf")
 
 
 def glu(gate: torch.Tensor, up: torch.Tensor, out: torch.Tensor, act: int):
@@ -403,7 +423,7 @@ def sample(logits: torch.Tensor, min_p: float, greedy: bool, seed: int,
            bump_len: bool = True, temperature: float = 1.0,
            cnt: torch.Tensor | None = None, batch: int = 1, *,
            top_k: int = 0, top_p: float = 1.0,
-           sel: torch.Tensor | None = None):
+           sel: torch.Tensor | None = None, blocks: int | None = None):
     """min-p / greedy sampler: parallel max + Gumbel-argmax; the
     last-arriving pick block commits the winner (no 1-thread fin
     launch).  gmax/pick are u64 scratch (zeroed once; the commit path
@@ -416,7 +436,15 @@ def sample(logits: torch.Tensor, min_p: float, greedy: bool, seed: int,
     threshold (``filter_probs`` semantics; ``min_p`` is then unused).
     ``sel`` is its scratch: int64, ``SAMPLE_SEL_WORDS`` per row, zeroed
     once and re-armed on device.  With both filters off the launch is
-    exactly the min-p / greedy one."""
+    exactly the min-p / greedy one.
+
+    ``blocks``: blocks per row of the max / pick launches (min-p / greedy
+    path only); ``None`` = the launcher's rule.  The winner is defined
+    over element indices, so every count gives the same token."""
+    if blocks is not None and (top_k > 0 or top_p < 1.0):
+        raise ValueError("blocks applies to the min-p / greedy launch only")
+    if blocks is not None and blocks < 1:
+        raise ValueError(f"blocks must be >= 1, got {blocks}")
     if top_k < 0:
         raise ValueError(f"top_k must be >= 0, got {top_k}")
     if not 0.0 < top_p <= 1.0:
@@ -466,7 +494,7 @@ def sample(logits: torch.Tensor, min_p: float, greedy: bool, seed: int,
         ctypes.c_uint64(seed), ctypes.c_float(inv_temp),
         _ptr(ctr), _ptr(gmax), _ptr(pick), _ptr(cnt),
         _ptr(next_token), _ptr(out_ring), _ptr(nout), _ptr(len_ptr),
-        1 if bump_len else 0, _stream()), "sample")
+        1 if bump_len else 0, int(blocks or 0), _stream()), "sample")
 
 
 # per-row sampler table (csrc/llm_ops.hip SAMP_*): 8 32-bit words per row
