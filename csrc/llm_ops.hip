@@ -1291,6 +1291,239 @@ extern "C" hipError_t launch_gemm_fp8_skinny(
 }
 
 // ====================================================================
+// MXFP4-native skinny GEMM (batched decode on single-copy fp4 engines):
+//   Y[B<=16, N] = sx_b * sum_k Xq[b,k] * (2^(E[n,k/32]-127) * W4[n,k])
+// The fp4 twin of k_gemm_fp8_skinny: the engine's MXFP4 weights (`*_q4`
+// / `*_e4`, exactly as k_quant_fp4_rows writes them) go straight into
+// v_mfma_scale_f32_16x16x128_f8f6f4 — no fp8 copy, no repack, no
+// dequantisation.  Activations are the e4m3 rows + per-row scale that
+// k_stage_quant_mx already produces.
+// ====================================================================
+
+typedef int i8v __attribute__((ext_vector_type(8)));
+
+// A operand of one K=128 step (8 VGPRs, L2-hot).  The 8-bit operand is
+// NOT 32 consecutive K per lane: VGPRs 0-3 of k-group g hold K-elements
+// [16g, 16g+16) of the step and VGPRs 4-7 hold [64+16g, 64+16g+16)
+// (measured on gfx950 with one-hot rows), so two 16 B loads 64 B apart.
+DEVINL i8v fp4sk_pack_x(u4v_ lo, u4v_ hi) {
+  return i8v{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3],
+             (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+}
+
+DEVINL i8v fp4sk_ld_x(const uint8_t* p) {
+  return fp4sk_pack_x(*(const u4v_*)p, *(const u4v_*)(p + 64));
+}
+
+// B operand: the 4-bit operand IS consecutive — k-group g holds the 32
+// K-elements [32g, 32g+32) of its weight row as e2m1 nibbles = ONE
+// non-temporal dwordx4 (the fp4 form reads 4 of the 8 operand VGPRs),
+// and the lane's scale byte covers exactly that MX block
+DEVINL i8v fp4sk_ld_w(const uint8_t* p) {
+  const u4v_ w = __builtin_nontemporal_load((const u4v_*)p);
+  return i8v{(int)w[0], (int)w[1], (int)w[2], (int)w[3], 0, 0, 0, 0};
+}
+
+// The instruction adds its 128 products on a grid set by the largest:
+// X elements far below their row's largest (e4m3 exponent field < 8,
+// i.e. under 2^-7 of it) lose low bits next to large ones — steps of
+// 2^-16 of the largest product, more than fp32 accumulation allows at
+// K = 128 (profiles/batch_fp4_skinny.md).  So every step runs TWO MFMAs
+// on accumulators of their own: the elements with exponent bit 3 set,
+// and the rest.  A masked-out element keeps its sign bit (+-0 * w).
+DEVINL i8v fp4sk_x_hi(i8v a) {
+  i8v r;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const uint32_t m = (uint32_t)a[i] & 0x40404040u;
+    r[i] = (int)((uint32_t)a[i] & (((m << 1) - (m >> 6)) | 0x80808080u));
+  }
+  return r;
+}
+
+DEVINL i8v fp4sk_x_lo(i8v a) {
+  i8v r;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const uint32_t m = (uint32_t)a[i] & 0x40404040u;
+    r[i] = (int)((uint32_t)a[i] & ~((m << 1) - (m >> 6)));
+  }
+  return r;
+}
+
+// A = e4m3 (cbsz 0) with the constant e8m0 scale 1.0 (127), B = e2m1
+// (blgp 4) with the lane's block scale in byte 0 of `sb`
+#define FP4SK_MFMA(a, b, c, sb)                                           \
+  __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 4, 0, 127, \
+                                                   0, sb)
+
+// one 16x16 output tile per wave; acc row = X row (B dim), col = W row.
+// A step is K=128 = one operand load and the MFMA pair above: the lane
+// in k-group g = lane>>4 supplies row lane&15, the weight K-elements
+// [k+32g, k+32g+32) — one whole MX block, so its scale byte belongs to
+// this lane alone — and the two 16-element X chunks the 8-bit layout
+// asks of it (fp4sk_ld_x).  A trip is four steps, K=512, on SIX
+// independent accumulator chains (four for the large X elements, two
+// for the small; the fp8 kernel's finding: two chains left waves parked
+// on memory); the up to three steps left over rotate through the same
+// chains, their loads issued step by step.  In a last partial step a
+// lane loads nothing for a block or chunk at or beyond k_hi and passes
+// zero data with scale 127.  grid.y splits K in whole 128-steps
+// (atomicAdd into the fp32 accbuf, epilogue in k_fp4_skinny_fin).
+extern "C" __global__ void __launch_bounds__(256)
+k_gemm_fp4_skinny(const uint8_t* __restrict__ Xq,
+                  const float* __restrict__ sx,
+                  const uint8_t* __restrict__ W4,
+                  const uint8_t* __restrict__ E, void* __restrict__ y,
+                  long ystride, const u16* __restrict__ res, long rstride,
+                  const u16* __restrict__ bias, float* __restrict__ accbuf,
+                  int out_f32, float softcap, int B, int N, int K) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int fr = lane & 15, g = lane >> 4;
+  const int asrc = fr < B ? fr : 0;  // padded A rows read row 0
+  const uint8_t* Xr = Xq + (size_t)asrc * K + g * 16;
+  const int SK = gridDim.y;
+  const int per = (((K + 127) / 128 + SK - 1) / SK) * 128;
+  const int k_lo = blockIdx.y * per;
+  int k_hi = k_lo + per;
+  if (k_hi > K) k_hi = K;
+  if (k_hi <= k_lo) return;
+  for (int n0 = (blockIdx.x * 4 + wave) * 16; n0 < N;
+       n0 += gridDim.x * 4 * 16) {
+    int wr = n0 + fr;
+    if (wr >= N) wr = N - 1;
+    const uint8_t* Wr = W4 + (size_t)wr * (K >> 1) + g * 16;
+    const uint8_t* Er = E + (size_t)wr * (K >> 5) + g;
+    f4v acc_a = {0.f, 0.f, 0.f, 0.f};
+    f4v acc_b = {0.f, 0.f, 0.f, 0.f};
+    f4v acc_c = {0.f, 0.f, 0.f, 0.f};
+    f4v acc_d = {0.f, 0.f, 0.f, 0.f};
+    f4v acc_e = {0.f, 0.f, 0.f, 0.f};  // small-exponent X elements
+    f4v acc_f = {0.f, 0.f, 0.f, 0.f};
+    int k = k_lo;
+    for (; k + 512 <= k_hi; k += 512) {
+      const i8v a0 = fp4sk_ld_x(Xr + k);
+      const i8v b0 = fp4sk_ld_w(Wr + (k >> 1));
+      const int s0 = Er[k >> 5];
+      const i8v a1 = fp4sk_ld_x(Xr + k + 128);
+      const i8v b1 = fp4sk_ld_w(Wr + (k >> 1) + 64);
+      const int s1 = Er[(k >> 5) + 4];
+      const i8v a2 = fp4sk_ld_x(Xr + k + 256);
+      const i8v b2 = fp4sk_ld_w(Wr + (k >> 1) + 128);
+      const int s2 = Er[(k >> 5) + 8];
+      const i8v a3 = fp4sk_ld_x(Xr + k + 384);
+      const i8v b3 = fp4sk_ld_w(Wr + (k >> 1) + 192);
+      const int s3 = Er[(k >> 5) + 12];
+      acc_a = FP4SK_MFMA(fp4sk_x_hi(a0), b0, acc_a, s0);
+      acc_e = FP4SK_MFMA(fp4sk_x_lo(a0), b0, acc_e, s0);
+      acc_b = FP4SK_MFMA(fp4sk_x_hi(a1), b1, acc_b, s1);
+      acc_f = FP4SK_MFMA(fp4sk_x_lo(a1), b1, acc_f, s1);
+      acc_c = FP4SK_MFMA(fp4sk_x_hi(a2), b2, acc_c, s2);
+      acc_e = FP4SK_MFMA(fp4sk_x_lo(a2), b2, acc_e, s2);
+      acc_d = FP4SK_MFMA(fp4sk_x_hi(a3), b3, acc_d, s3);
+      acc_f = FP4SK_MFMA(fp4sk_x_lo(a3), b3, acc_f, s3);
+    }
+    // under four steps are left (the last maybe partial): unrolled, so
+    // the rotation through the chains is register renaming
+#pragma unroll
+    for (int j = 0; j < 4; j++, k += 128) {
+      if (k >= k_hi) break;
+      const u4v_ z = {0u, 0u, 0u, 0u};
+      u4v_ lo = z, hi = z;
+      i8v b = {0, 0, 0, 0, 0, 0, 0, 0};
+      int s = 127;  // 0xFF would be NaN: never a stray scale byte
+      if (k + g * 16 < k_hi) lo = *(const u4v_*)(Xr + k);
+      if (k + 64 + g * 16 < k_hi) hi = *(const u4v_*)(Xr + k + 64);
+      if (k + g * 32 < k_hi) {
+        b = fp4sk_ld_w(Wr + (k >> 1));
+        s = Er[k >> 5];
+      }
+      const i8v a = fp4sk_pack_x(lo, hi);
+      acc_a = FP4SK_MFMA(fp4sk_x_hi(a), b, acc_a, s);
+      acc_e = FP4SK_MFMA(fp4sk_x_lo(a), b, acc_e, s);
+      const f4v ta = acc_a, te = acc_e;
+      acc_a = acc_b; acc_b = acc_c; acc_c = acc_d; acc_d = ta;
+      acc_e = acc_f; acc_f = te;
+    }
+    const int col = n0 + fr;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int b = g * 4 + r;
+      if (b < B && col < N) {
+        float v = ((acc_a[r] + acc_b[r]) + (acc_c[r] + acc_d[r])) +
+                  (acc_e[r] + acc_f[r]);
+        if (SK > 1) {
+          atomicAdd(accbuf + (size_t)b * N + col, v);
+        } else {
+          v *= sx[b];
+          if (softcap > 0.f) v = softcap * tanhf(v / softcap);
+          if (bias) v += b2f(bias[col]);
+          if (res) v += b2f(res[(size_t)b * rstride + col]);
+          if (out_f32) ((float*)y)[(size_t)b * ystride + col] = v;
+          else ((u16*)y)[(size_t)b * ystride + col] = f2b(v);
+        }
+      }
+    }
+  }
+}
+
+// SK>1 epilogue: raw sums -> sx_b, softcap, bias, res -> y (the weight
+// scales already rode inside the MFMA)
+extern "C" __global__ void __launch_bounds__(256)
+k_fp4_skinny_fin(const float* __restrict__ accbuf,
+                 const float* __restrict__ sx, void* __restrict__ y,
+                 long ystride, const u16* __restrict__ res, long rstride,
+                 const u16* __restrict__ bias, int out_f32, float softcap,
+                 int B, int N) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)B * N) return;
+  const int b = (int)(i / N), col = (int)(i % N);
+  float v = accbuf[(size_t)b * N + col] * sx[b];
+  if (softcap > 0.f) v = softcap * tanhf(v / softcap);
+  if (bias) v += b2f(bias[col]);
+  if (res) v += b2f(res[(size_t)b * rstride + col]);
+  if (out_f32) ((float*)y)[(size_t)b * ystride + col] = v;
+  else ((u16*)y)[(size_t)b * ystride + col] = f2b(v);
+}
+
+// W4: [N, K/2] packed e2m1 (element 2j = low nibble of byte j), E:
+// [N, K/32] e8m0.  Split-K by the fp8 launcher's rule (accbuf given and
+// < 512 blocks -> up to 8 slices), in whole 128-steps.
+extern "C" hipError_t launch_gemm_fp4_skinny(
+    const void* Xq, const void* sx, const void* W4, const void* E, void* y,
+    long ystride, const void* res, long rstride, const void* bias,
+    void* accbuf, int out_f32, float softcap, int B, int N, int K,
+    hipStream_t stream) {
+  if (B < 1 || B > 16 || N < 1 || K < 32 || K % 32 != 0)
+    return hipErrorInvalidValue;
+  int blocks = (N + 63) / 64;
+  if (blocks > 1024) blocks = 1024;
+  int sk = 1;
+  if (accbuf && blocks < 512) {
+    sk = 512 / blocks;
+    if (sk > 8) sk = 8;
+    const int steps = (K + 127) / 128;
+    if (sk > steps) sk = steps;
+  }
+  const long total = (long)B * N;
+  if (sk > 1)
+    hipLaunchKernelGGL(k_zero_f32, dim3((uint32_t)((total + 1023) / 1024)),
+                       dim3(256), 0, stream, (float*)accbuf, total);
+  hipLaunchKernelGGL(k_gemm_fp4_skinny, dim3(blocks, sk), dim3(256), 0,
+                     stream, (const uint8_t*)Xq, (const float*)sx,
+                     (const uint8_t*)W4, (const uint8_t*)E, y, ystride,
+                     (const u16*)res, rstride, (const u16*)bias,
+                     (float*)accbuf, out_f32, softcap, B, N, K);
+  if (sk > 1)
+    hipLaunchKernelGGL(k_fp4_skinny_fin,
+                       dim3((uint32_t)((total + 255) / 256)), dim3(256), 0,
+                       stream, (const float*)accbuf, (const float*)sx, y,
+                       ystride, (const u16*)res, rstride, (const u16*)bias,
+                       out_f32, softcap, B, N);
+  return hipGetLastError();
+}
+
+// ====================================================================
 // MXFP4 GEMV: y[N] = W4[N,K] @ stage(x)[K] (+res); 2 fp4/byte with one
 // e8m0 scale per 32 elements.  Same packed structure as the fp8 GEMV
 // (fp32 x staging or XDIR direct reads feeding v_pk_fma_f32) — the

@@ -72,12 +72,17 @@ class GPUModel:
                  dtype: str = "bf16", max_seq: Optional[int] = 4096,
                  prefill_chunk: int = 2048, device: Optional[str] = None,
                  seed: int = 0, force_tp_path: bool = False,
-                 kv_dtype: str = "bf16", max_batch: int = 1):
+                 kv_dtype: str = "bf16", max_batch: int = 1,
+                 batch_fp4: Optional[bool] = None):
         """``max_seq=None`` sizes the KV pool from FREE HBM after the
         weights land (288 GB per MI355X — SURVEY §5 long-context), capped
         at config.max_position_embeddings.  ``max_batch>1`` allocates
         per-sequence KV pools for lockstep batched decode
-        (prefill_batch/decode_batch; beyond-parity serving capability)."""
+        (prefill_batch/decode_batch; beyond-parity serving capability).
+        ``batch_fp4`` (None = env LLM_BATCH_FP4, default off) runs the
+        lockstep steps of a ``dtype="fp4"``, ``max_batch>1`` engine on
+        the MXFP4 weights themselves (`_proj_skinny4`) and drops the fp8
+        copy; ignored for every other engine."""
         if not torch.cuda.is_available():
             raise RuntimeError("GPUModel requires a GPU (MI355X)")
         self.config = config
@@ -96,6 +101,16 @@ class GPUModel:
         # fp4 + batch pools: the skinny MFMA GEMM consumes fp8, so keep
         # the fp8 copy only then; max_batch=1 fp4 engines are SINGLE-COPY
         self.keep_fp8 = (dtype == "fp8") or (self.wq4 and max_batch > 1)
+        # opt-in: batched steps on the MXFP4 copy itself (the scaled
+        # fp8 x fp4 MFMA skinny GEMM) — the engine stays single-copy
+        if batch_fp4 is None:
+            import os as _os
+            batch_fp4 = _os.environ.get("LLM_BATCH_FP4", "0").strip() \
+                not in ("", "0")
+        self.batch_fp4 = bool(batch_fp4 and self.wq4 and max_batch > 1
+                              and not config.is_moe)
+        if self.batch_fp4:
+            self.keep_fp8 = False
         if kv_dtype not in ("bf16", "fp8"):
             raise ValueError(f"unsupported kv_dtype {kv_dtype!r}")
         self.kv_dtype = kv_dtype
@@ -1831,8 +1846,10 @@ class GPUModel:
         bt_logits[:B], then the sampling tail.  fp8 weights take a fused
         stack (`_batch_layers_fused`) — the skinny fp8 MFMA GEMM up to
         B=16, or with LLM_BATCH_MX_MAX the multi-x GEMV (one weight
-        stream feeds B accumulators); otherwise the layer stack runs as
-        M=B-row MFMA GEMMs.  Graph-replayable (all state device-side)."""
+        stream feeds B accumulators); ``batch_fp4`` engines take the same
+        stack on their MXFP4 weights (`_proj_skinny4`); otherwise the
+        layer stack runs as M=B-row MFMA GEMMs.  Graph-replayable (all
+        state device-side)."""
         # measured (profiles/decode_kernels_r02.md): the SKINNY fp8 MFMA
         # GEMM wins at every B (even B=2: 1.34 vs the multi-x GEMV's
         # 1.44 ms — the GEMV is VALU-ISSUE-bound, 64 irreducible
@@ -1841,7 +1858,12 @@ class GPUModel:
         import os as _os  # noqa: delayed so env changes apply per call
         cfg = self.config
         mx_max = int(_os.environ.get("LLM_BATCH_MX_MAX", "0"))
-        if (self.fp8 and B <= mx_max and not cfg.attention_bias
+        if self.batch_fp4 and B <= 16:
+            # single-copy fp4 engine: the skinny GEMM on the MXFP4
+            # weights (the multi-x GEMV needs the fp8 copy: not taken)
+            self._batch_layers_fused(B, partial(self._proj_skinny4, B),
+                                     sfx=("_q4", "_e4"))
+        elif (self.fp8 and B <= mx_max and not cfg.attention_bias
                 and not self.moe):
             self._batch_layers_fused(B, partial(self._proj_mx, B))
         elif self.fp8 and B <= 16 and not self.moe:
@@ -1857,7 +1879,10 @@ class GPUModel:
         self._layers_forward(B, batch_attn=True)
         ho.rmsnorm(self.b_h[:B], self.g_final, self.b_xn[:B],
                    eps=cfg.rms_norm_eps)
-        if self.fp8:
+        if self.wq4 and not self.keep_fp8:
+            ho.gemm_fp4w(self.b_xn[:B], self.lm_head_q4, self.lm_head_e4,
+                         self.bt_logits[:B], accbuf=self.b_gemm_acc)
+        elif self.fp8:
             ho.quant_fp8(self.b_xn[:B], self.b_xq, self.b_sx)
             ho.gemm_fp8(self.b_xq, self.b_sx, self.lm_head_q,
                         self.lm_head_s, self.bt_logits[:B], B, self.H,
@@ -1886,12 +1911,25 @@ class GPUModel:
                            rstride=N if res is not None else 0, bias=bias,
                            softcap=softcap, accbuf=self.b_gemm_acc)
 
-    def _batch_layers_fused(self, B: int, proj):
-        """Fused lockstep layer stack (fp8): mirrors `_decode_layers`'
-        4-5 projections per layer over B rows, each one ``proj(wq, ws, x,
-        xstride, y, K, N, res=, bias=, softcap=, **stage_kw)`` with the
-        norm / embed gather / GLU as its staging op (`_proj_mx` or
-        `_proj_skinny`)."""
+    def _proj_skinny4(self, B, wq4, we4, x, xstride, y, K, N, *, res=None,
+                      bias=None, softcap=0.0, **stage_kw):
+        """`_proj_skinny` on the MXFP4 weights themselves: the same
+        staging + e4m3 row quant, then the scaled fp8 x fp4 MFMA skinny
+        GEMM (half the weight bytes, no fp8 copy)."""
+        ho.stage_quant_mx(x, xstride, self.b_xq, self.b_sx, B, K, **stage_kw)
+        ho.gemm_fp4_skinny(self.b_xq, self.b_sx, wq4, we4, y, B, N, res=res,
+                           rstride=N if res is not None else 0, bias=bias,
+                           softcap=softcap, accbuf=self.b_gemm_acc)
+
+    def _batch_layers_fused(self, B: int, proj, sfx=("_q", "_s")):
+        """Fused lockstep layer stack (fp8 / MXFP4): mirrors
+        `_decode_layers`' 4-5 projections per layer over B rows, each one
+        ``proj(wq, ws, x, xstride, y, K, N, res=, bias=, softcap=,
+        **stage_kw)`` with the norm / embed gather / GLU as its staging
+        op (`_proj_mx`, `_proj_skinny` or `_proj_skinny4`).  ``sfx``
+        names the weight pair ``proj`` consumes: ("_q", "_s") the fp8
+        copy, ("_q4", "_e4") the MXFP4 one."""
+        qs, ss = sfx
         cfg = self.config
         eps = cfg.rms_norm_eps
         H, I = self.H, self.inter_l
@@ -1923,8 +1961,8 @@ class GPUModel:
                           escale=cfg.embed_scale)
             else:
                 st = dict(stage=ho.STAGE_NORM, g=lw["g_in"], eps=eps)
-            proj(lw["wqkv_q"], lw["wqkv_s"], x, xstride, self.bt_qkv, H,
-                 qkvw, bias=lw.get("bqkv"), **st)
+            proj(lw["wqkv" + qs], lw["wqkv" + ss], x, xstride, self.bt_qkv,
+                 H, qkvw, bias=lw.get("bqkv"), **st)
             prev = lw
             ho.attn_dec(self.bt_qkv, self.k_cache[i], self.v_cache[i],
                         self.b_att[0], self.bt_lens, self.cos_t, self.sin_t,
@@ -1934,25 +1972,27 @@ class GPUModel:
                         split=self.attn_split, kS=self.k_scale[i],
                         vS=self.v_scale[i], batch=B, merge=self.attn_merge)
             if self.gemma:
-                proj(lw["wo_q"], lw["wo_s"], self.b_att, nhh, t1, nhh, H)
-                proj(lw["wgu_q"], lw["wgu_s"], t1, H, gu, H, 2 * I,
+                proj(lw["wo" + qs], lw["wo" + ss], self.b_att, nhh, t1, nhh,
+                     H)
+                proj(lw["wgu" + qs], lw["wgu" + ss], t1, H, gu, H, 2 * I,
                      **norm2(lw["g_post"], lw["g_preffn"]))
                 h, hb = hb, h
-                proj(lw["wdown_q"], lw["wdown_s"], gu, 2 * I, t2, I, H,
-                     **glu)
+                proj(lw["wdown" + qs], lw["wdown" + ss], gu, 2 * I, t2, I,
+                     H, **glu)
             else:
-                proj(lw["wo_q"], lw["wo_s"], self.b_att, nhh, h, nhh, H,
-                     res=h)
-                proj(lw["wgu_q"], lw["wgu_s"], h, H, gu, H, 2 * I,
+                proj(lw["wo" + qs], lw["wo" + ss], self.b_att, nhh, h, nhh,
+                     H, res=h)
+                proj(lw["wgu" + qs], lw["wgu" + ss], h, H, gu, H, 2 * I,
                      stage=ho.STAGE_NORM, g=lw["g_post"], eps=eps)
-                proj(lw["wdown_q"], lw["wdown_s"], gu, 2 * I, h, I, H,
-                     res=h, **glu)
+                proj(lw["wdown" + qs], lw["wdown" + ss], gu, 2 * I, h, I,
+                     H, res=h, **glu)
         if self.gemma:
             x, st = t2, norm2(self.layers[-1]["g_postffn"], self.g_final)
         else:
             x, st = h, dict(stage=ho.STAGE_NORM, g=self.g_final, eps=eps)
-        proj(self.lm_head_q, self.lm_head_s, x, H, self.bt_logits, H,
-             self.vocab_l, softcap=self.final_softcap, **st)
+        proj(getattr(self, "lm_head" + qs), getattr(self, "lm_head" + ss),
+             x, H, self.bt_logits, H, self.vocab_l,
+             softcap=self.final_softcap, **st)
 
     def prefill_batch(self, prompts) -> None:
         """Prefill B prompts (RAGGED lengths allowed) into per-sequence

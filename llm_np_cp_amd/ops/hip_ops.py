@@ -126,6 +126,12 @@ _SIGS = {
                                ctypes.c_int,
                                ctypes.c_float] + [ctypes.c_int] * 3 +
                               [ctypes.c_void_p],
+    "launch_gemm_fp4_skinny": [ctypes.c_void_p] * 5 + [ctypes.c_long] +
+                              [ctypes.c_void_p, ctypes.c_long] +
+                              [ctypes.c_void_p, ctypes.c_void_p,
+                               ctypes.c_int,
+                               ctypes.c_float] + [ctypes.c_int] * 3 +
+                              [ctypes.c_void_p],
     "launch_gemv_fp8_mx": [ctypes.c_void_p] * 3 + [ctypes.c_long] +
                           [ctypes.c_void_p, ctypes.c_long] +
                           [ctypes.c_void_p] * 3 + [ctypes.c_long] +
@@ -1113,6 +1119,40 @@ def gemm_fp8_skinny(xq: torch.Tensor, sx: torch.Tensor, Wq: torch.Tensor,
         ctypes.c_long(ystride), _ptr(res), ctypes.c_long(rstride),
         _ptr(bias), _ptr(accbuf), out_f32, ctypes.c_float(softcap),
         B, N, K, _stream()), "gemm_fp8_skinny")
+
+
+def gemm_fp4_skinny(xq: torch.Tensor, sx: torch.Tensor, Wq4: torch.Tensor,
+                    We4: torch.Tensor, y: torch.Tensor, B: int,
+                    ystride: int, res: torch.Tensor | None = None,
+                    rstride: int = 0, bias: torch.Tensor | None = None,
+                    softcap: float = 0.0,
+                    accbuf: torch.Tensor | None = None):
+    """Y[B<=16, N] = sx_b * Xq @ dequant(W4)^T: the skinny GEMM on the
+    MXFP4 weights themselves (Wq4: N x K/2 packed bytes, We4: N x K/32
+    e8m0 bytes) — one scaled 16x16x128 fp8 x fp4 MFMA tile per wave, W4
+    nt-streamed once at half the fp8 bytes.  xq / sx come from
+    ``stage_quant_mx``; accbuf as in ``gemm_fp8_skinny``."""
+    N = Wq4.shape[0]
+    K = Wq4.shape[1] * 2
+    if not 1 <= B <= 16:
+        raise ValueError(f"gemm_fp4_skinny: B={B} outside 1..16")
+    if K % 32 != 0:
+        raise ValueError(f"gemm_fp4_skinny: K={K} is not a multiple of 32")
+    if We4.numel() * 32 < N * K:
+        raise ValueError(f"gemm_fp4_skinny: scales {tuple(We4.shape)} do "
+                         f"not cover weights ({N}, {K})")
+    if not (Wq4.is_contiguous() and We4.is_contiguous()):
+        raise ValueError("gemm_fp4_skinny: weight rows must be contiguous")
+    if xq.numel() < B * K or sx.numel() < B:
+        raise ValueError("gemm_fp4_skinny: xq / sx smaller than B rows")
+    out_f32 = 1 if y.dtype == torch.float32 else 0
+    if accbuf is not None and accbuf.numel() < B * N:
+        accbuf = None
+    _check(lib().launch_gemm_fp4_skinny(
+        _ptr(xq), _ptr(sx), _ptr(Wq4), _ptr(We4), _ptr(y),
+        ctypes.c_long(ystride), _ptr(res), ctypes.c_long(rstride),
+        _ptr(bias), _ptr(accbuf), out_f32, ctypes.c_float(softcap),
+        B, N, K, _stream()), "gemm_fp4_skinny")
 
 
 def gemm_fp4w(X: torch.Tensor, Wq4: torch.Tensor, We4: torch.Tensor,
