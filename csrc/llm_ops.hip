@@ -1524,6 +1524,258 @@ extern "C" hipError_t launch_gemm_fp4_skinny(
 }
 
 // ====================================================================
+// bf16 skinny MFMA GEMM (opt-in batched decode on bf16 engines):
+//   Y[B<=16, N] = X[B,K] @ W[N,K]^T, bf16 operands, fp32 accumulation
+// on v_mfma_f32_16x16x32_bf16.  The bf16 twin of k_gemm_fp8_skinny with
+// three differences: X is read IN PLACE with an element stride (a RAW
+// projection needs no staging launch), a paired-row GLU epilogue
+// (W = [gate; up]) and a DETERMINISTIC split-K (per-slice partial
+// tiles, summed in slice order by k_bf16_skinny_fin — no atomics, no
+// zeroing launch).
+//   1. k_stage_rows_bf16: per sequence row, NORM / NORM2 / NORM_EMBED
+//      -> xs[B,K] rounded to bf16 (no quantisation).
+//   2. k_gemm_bf16_skinny<GLU> (+ k_bf16_skinny_fin when split).
+// ====================================================================
+
+// these kernels are compiled without the packed fp32 VALU forms
+// (v_pk_add/mul/fma_f32): scalar fp32 only, the same IEEE results
+#if defined(__HIP_DEVICE_COMPILE__)
+#define BSK_KERNEL \
+  __global__ void __launch_bounds__(256) \
+      __attribute__((target("no-packed-fp32-ops")))
+#else  // the host pass does not know the device feature
+#define BSK_KERNEL __global__ void __launch_bounds__(256)
+#endif
+
+extern "C" BSK_KERNEL
+k_stage_rows_bf16(const u16* __restrict__ x, long xstride,
+                  const u16* __restrict__ x2, long x2stride,
+                  const float* __restrict__ g, const float* __restrict__ g2,
+                  u16* __restrict__ xs, u16* __restrict__ hout,
+                  long hstride, int K, int B, int stage, int act, float eps,
+                  float escale) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* red = (float*)(smem + (size_t)K * 4);
+  const int b = blockIdx.x;
+  const u16* xb = x + (size_t)b * xstride;
+  if (stage == STAGE_NORM_EMBED)
+    xb = x + (size_t)((const int*)x2)[b] * (size_t)K;
+  const u16* x2b = (stage == STAGE_NORM_EMBED || x2 == nullptr)
+                       ? nullptr : x2 + (size_t)b * x2stride;
+  u16* houtb = hout ? hout + (size_t)b * hstride : nullptr;
+  gemv_stage_mx_row<true>(smem, 0, xb, x2b, g, g2, houtb, K, 1, stage,
+                          act, eps, escale, red, true);
+  __syncthreads();
+  const float* xf = (const float*)smem;
+  u16* o = xs + (size_t)b * K;
+  for (int i = threadIdx.x * 8; i < K; i += 2048) {
+    s8v v;
+#pragma unroll
+    for (int j = 0; j < 8; j++) v[j] = (short)f2b(xf[i + j]);
+    *(s8v*)(o + i) = v;
+  }
+}
+
+extern "C" hipError_t launch_stage_rows_bf16(
+    const void* x, long xstride, const void* x2, long x2stride,
+    const void* g, const void* g2, void* xs, void* hout, long hstride,
+    int K, int B, int stage, int act, float eps, float escale,
+    hipStream_t stream) {
+  size_t lds = (size_t)K * 4 + 64;
+  if (lds > 160 * 1024 || K % 16 != 0 || B < 1) return hipErrorInvalidValue;
+  if (stage != STAGE_NORM && stage != STAGE_NORM2 &&
+      stage != STAGE_NORM_EMBED)
+    return hipErrorInvalidValue;
+  static bool raised = false;
+  if (lds > 65536 && !raised) {
+    hipFuncSetAttribute((const void*)&k_stage_rows_bf16,
+                        hipFuncAttributeMaxDynamicSharedMemorySize,
+                        160 * 1024);
+    raised = true;
+  }
+  hipLaunchKernelGGL(k_stage_rows_bf16, dim3(B), dim3(256), lds, stream,
+                     (const u16*)x, xstride, (const u16*)x2, x2stride,
+                     (const float*)g, (const float*)g2, (u16*)xs,
+                     (u16*)hout, hstride, K, B, stage, act, eps, escale);
+  return hipGetLastError();
+}
+
+#define BSK_MFMA(a, b, c) \
+  __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0)
+
+// one 16x16 output tile per wave (GLU: the gate tile and the up tile of
+// the same 16 output columns); acc row = X row (B dim), col = W row.
+// The lane in k-group g = lane>>4 supplies the 8 consecutive bf16
+// [k+8g, k+8g+8) of row lane&15: ONE 16 B load per operand per MFMA, W
+// non-temporal (streamed once), X plain (<= 64 KB, L2-hot).  A trip is
+// K=256: all of its loads are issued before its first MFMA, and its
+// eight MFMAs run on FOUR independent accumulator chains per tile (the
+// fp8 kernel's finding: two chains left waves parked on memory).  The
+// remainder runs in K=32 steps.  grid.y splits K in whole 32-chunks;
+// slice s stores its raw fp32 tile to accbuf[s][B][N] with plain stores
+// (zeros when its K range is empty), k_bf16_skinny_fin does the rest.
+template <bool GLU>
+BSK_KERNEL
+k_gemm_bf16_skinny(const u16* __restrict__ X, long xstride,
+                   const u16* __restrict__ W, void* __restrict__ y,
+                   long ystride, const u16* __restrict__ res, long rstride,
+                   const u16* __restrict__ bias, float* __restrict__ accbuf,
+                   int out_f32, float softcap, int act, int B, int N,
+                   int K) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int fr = lane & 15, g = lane >> 4;
+  const int asrc = fr < B ? fr : 0;  // padded A rows read row 0
+  const u16* Xr = X + (size_t)asrc * xstride + g * 8;
+  const int NO = GLU ? N >> 1 : N;   // output columns
+  const int SK = gridDim.y;
+  const int per = ((K / 32 + SK - 1) / SK) * 32;
+  int k_lo = blockIdx.y * per;
+  if (k_lo > K) k_lo = K;
+  int k_hi = k_lo + per;
+  if (k_hi > K) k_hi = K;
+  for (int n0 = (blockIdx.x * 4 + wave) * 16; n0 < NO;
+       n0 += gridDim.x * 4 * 16) {
+    int wr = n0 + fr;
+    if (wr >= NO) wr = NO - 1;
+    const u16* Wg = W + (size_t)wr * K + g * 8;
+    const u16* Wu = Wg + (size_t)NO * K;  // GLU: the paired up row
+    f4v ag[4], au[4];
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+      ag[c] = (f4v){0.f, 0.f, 0.f, 0.f};
+      au[c] = (f4v){0.f, 0.f, 0.f, 0.f};
+    }
+    int k = k_lo;
+    for (; k + 256 <= k_hi; k += 256) {
+      s8v a[8], bg[8], bu[8];
+#pragma unroll
+      for (int j = 0; j < 8; j++) {
+        a[j] = *(const s8v*)(Xr + k + 32 * j);
+        bg[j] = __builtin_nontemporal_load((const s8v*)(Wg + k + 32 * j));
+        if (GLU)
+          bu[j] = __builtin_nontemporal_load((const s8v*)(Wu + k + 32 * j));
+      }
+      // keep the scheduler from sinking loads between the MFMAs: the
+      // whole trip is in flight before the first one waits
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int j = 0; j < 8; j++) {
+        ag[j & 3] = BSK_MFMA(a[j], bg[j], ag[j & 3]);
+        if (GLU) au[j & 3] = BSK_MFMA(a[j], bu[j], au[j & 3]);
+      }
+    }
+    for (; k < k_hi; k += 32) {
+      const s8v a0 = *(const s8v*)(Xr + k);
+      ag[0] = BSK_MFMA(
+          a0, __builtin_nontemporal_load((const s8v*)(Wg + k)), ag[0]);
+      if (GLU)
+        au[0] = BSK_MFMA(
+            a0, __builtin_nontemporal_load((const s8v*)(Wu + k)), au[0]);
+    }
+    const int col = n0 + fr;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int b = g * 4 + r;
+      if (b >= B || col >= NO) continue;
+      float v = (ag[0][r] + ag[1][r]) + (ag[2][r] + ag[3][r]);
+      float u = (au[0][r] + au[1][r]) + (au[2][r] + au[3][r]);
+      if (SK > 1) {
+        float* p = accbuf + ((size_t)blockIdx.y * B + b) * N + col;
+        p[0] = v;
+        if (GLU) p[NO] = u;
+      } else if (GLU) {
+        ((u16*)y)[(size_t)b * ystride + col] =
+            glu_act(b2f(f2b(v)), b2f(f2b(u)), act);
+      } else {
+        if (softcap > 0.f) v = softcap * tanhf(v / softcap);
+        if (bias) v += b2f(bias[col]);
+        if (res) v += b2f(res[(size_t)b * rstride + col]);
+        if (out_f32) ((float*)y)[(size_t)b * ystride + col] = v;
+        else ((u16*)y)[(size_t)b * ystride + col] = f2b(v);
+      }
+    }
+  }
+}
+
+// SK>1 epilogue: sum the slices in order s = 0..SK-1, then the same
+// epilogue as the unsplit kernel (glu: columns n and n + N/2)
+extern "C" BSK_KERNEL
+k_bf16_skinny_fin(const float* __restrict__ accbuf, void* __restrict__ y,
+                  long ystride, const u16* __restrict__ res, long rstride,
+                  const u16* __restrict__ bias, int out_f32, float softcap,
+                  int glu, int act, int B, int N, int SK) {
+  const int NO = glu ? N >> 1 : N;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)B * NO) return;
+  const int b = (int)(i / NO), col = (int)(i % NO);
+  const float* p = accbuf + (size_t)b * N + col;
+  float v = 0.f, u = 0.f;
+  for (int s = 0; s < SK; s++, p += (size_t)B * N) {
+    v += p[0];
+    if (glu) u += p[NO];
+  }
+  if (glu) {
+    ((u16*)y)[(size_t)b * ystride + col] =
+        glu_act(b2f(f2b(v)), b2f(f2b(u)), act);
+    return;
+  }
+  if (softcap > 0.f) v = softcap * tanhf(v / softcap);
+  if (bias) v += b2f(bias[col]);
+  if (res) v += b2f(res[(size_t)b * rstride + col]);
+  if (out_f32) ((float*)y)[(size_t)b * ystride + col] = v;
+  else ((u16*)y)[(size_t)b * ystride + col] = f2b(v);
+}
+
+// W: [N, K] bf16 row-major; X rows `xstride` elements apart (16 B
+// aligned).  glu = I > 0: N = 2I, y gets I columns.  Split-K by the fp8
+// launcher's rule (accbuf given and < 512 blocks -> up to 8 slices of
+// whole 32-chunks), further limited to the `acc_cap` floats of accbuf.
+extern "C" hipError_t launch_gemm_bf16_skinny(
+    const void* X, long xstride, const void* W, void* y, long ystride,
+    const void* res, long rstride, const void* bias, void* accbuf,
+    long acc_cap, int out_f32, float softcap, int glu, int act, int B,
+    int N, int K, hipStream_t stream) {
+  if (B < 1 || B > 16 || N < 1 || K < 32 || K % 32 != 0 || xstride % 8 != 0)
+    return hipErrorInvalidValue;
+  if (glu && (N != 2 * glu || res || bias || softcap > 0.f || out_f32))
+    return hipErrorInvalidValue;
+  const int NO = glu ? glu : N;
+  int blocks = (NO + 63) / 64;
+  if (blocks > 1024) blocks = 1024;
+  int sk = 1;
+  if (accbuf && blocks < 512) {
+    sk = 512 / blocks;
+    if (sk > 8) sk = 8;
+    const int chunks = K / 32;
+    if (sk > chunks) sk = chunks;
+    const long fit = acc_cap / ((long)B * N);
+    if (sk > fit) sk = (int)fit;
+    if (sk > 1) {  // no empty slice
+      const int per = (chunks + sk - 1) / sk;
+      sk = (chunks + per - 1) / per;
+    }
+    if (sk < 1) sk = 1;
+  }
+#define BSK_CASE(GLUV)                                                      \
+  hipLaunchKernelGGL((k_gemm_bf16_skinny<GLUV>), dim3(blocks, sk),          \
+                     dim3(256), 0, stream, (const u16*)X, xstride,          \
+                     (const u16*)W, y, ystride, (const u16*)res, rstride,   \
+                     (const u16*)bias, (float*)accbuf, out_f32, softcap,    \
+                     act, B, N, K)
+  if (glu) BSK_CASE(true); else BSK_CASE(false);
+#undef BSK_CASE
+  if (sk > 1) {
+    const long total = (long)B * NO;
+    hipLaunchKernelGGL(k_bf16_skinny_fin,
+                       dim3((uint32_t)((total + 255) / 256)), dim3(256), 0,
+                       stream, (const float*)accbuf, y, ystride,
+                       (const u16*)res, rstride, (const u16*)bias, out_f32,
+                       softcap, glu, act, B, N, sk);
+  }
+  return hipGetLastError();
+}
+
+// ====================================================================
 // MXFP4 GEMV: y[N] = W4[N,K] @ stage(x)[K] (+res); 2 fp4/byte with one
 // e8m0 scale per 32 elements.  Same packed structure as the fp8 GEMV
 // (fp32 x staging or XDIR direct reads feeding v_pk_fma_f32) — the

@@ -73,7 +73,8 @@ class GPUModel:
                  prefill_chunk: int = 2048, device: Optional[str] = None,
                  seed: int = 0, force_tp_path: bool = False,
                  kv_dtype: str = "bf16", max_batch: int = 1,
-                 batch_fp4: Optional[bool] = None):
+                 batch_fp4: Optional[bool] = None,
+                 batch_skinny: Optional[bool] = None):
         """``max_seq=None`` sizes the KV pool from FREE HBM after the
         weights land (288 GB per MI355X — SURVEY §5 long-context), capped
         at config.max_position_embeddings.  ``max_batch>1`` allocates
@@ -82,7 +83,11 @@ class GPUModel:
         ``batch_fp4`` (None = env LLM_BATCH_FP4, default off) runs the
         lockstep steps of a ``dtype="fp4"``, ``max_batch>1`` engine on
         the MXFP4 weights themselves (`_proj_skinny4`) and drops the fp8
-        copy; ignored for every other engine."""
+        copy; ignored for every other engine.  ``batch_skinny`` (None =
+        env LLM_BATCH_SKINNY, default off) runs the lockstep steps of a
+        bf16, ``max_batch>1``, single-GPU, non-MoE engine up to B = 16
+        on the bf16 skinny MFMA GEMM (`_proj_skinny_bf16`); ignored for
+        every other engine."""
         if not torch.cuda.is_available():
             raise RuntimeError("GPUModel requires a GPU (MI355X)")
         self.config = config
@@ -111,6 +116,12 @@ class GPUModel:
                               and not config.is_moe)
         if self.batch_fp4:
             self.keep_fp8 = False
+        if batch_skinny is None:
+            import os as _os
+            batch_skinny = _os.environ.get("LLM_BATCH_SKINNY", "0").strip() \
+                not in ("", "0")
+        self.batch_skinny = bool(batch_skinny and dtype == "bf16"
+                                 and max_batch > 1 and not config.is_moe)
         if kv_dtype not in ("bf16", "fp8"):
             raise ValueError(f"unsupported kv_dtype {kv_dtype!r}")
         self.kv_dtype = kv_dtype
@@ -126,6 +137,7 @@ class GPUModel:
             if config.model_type == "gemma2":
                 raise ValueError("MoE is a llama-family (Mixtral) feature")
         self.rank, self.world = tpu.init_distributed()
+        self.batch_skinny = self.batch_skinny and self.world == 1
         # exercise the TP code path on 1 GPU (collectives no-op at
         # world=1, partial sums are then exact) — used by tests
         self.tp_branch = self.world > 1 or force_tp_path
@@ -597,6 +609,10 @@ class GPUModel:
             self.bt_t1 = torch.zeros(B, H, **bf)
             self.bt_t2 = torch.zeros(B, H, **bf)
             self.bt_hb = torch.zeros(B, H, **bf)
+            if self.batch_skinny:
+                # normed rows of the bf16 skinny GEMM (K = H always: the
+                # RAW projections read their input in place)
+                self.bt_xs = torch.zeros(16, H, **bf)
 
         self.act = 0 if cfg.hidden_act == "silu" else 1
         self.gemma = cfg.model_type == "gemma2"
@@ -1858,7 +1874,11 @@ class GPUModel:
         import os as _os  # noqa: delayed so env changes apply per call
         cfg = self.config
         mx_max = int(_os.environ.get("LLM_BATCH_MX_MAX", "0"))
-        if self.batch_fp4 and B <= 16:
+        if self.batch_skinny and B <= 16:
+            # bf16 weights as they are; the GLU rides in the wgu GEMM
+            self._batch_layers_fused(B, partial(self._proj_skinny_bf16, B),
+                                     sfx=("", ""), glu_epilogue=True)
+        elif self.batch_fp4 and B <= 16:
             # single-copy fp4 engine: the skinny GEMM on the MXFP4
             # weights (the multi-x GEMV needs the fp8 copy: not taken)
             self._batch_layers_fused(B, partial(self._proj_skinny4, B),
@@ -1921,14 +1941,32 @@ class GPUModel:
                            rstride=N if res is not None else 0, bias=bias,
                            softcap=softcap, accbuf=self.b_gemm_acc)
 
-    def _batch_layers_fused(self, B: int, proj, sfx=("_q", "_s")):
+    def _proj_skinny_bf16(self, B, w, _w, x, xstride, y, K, N, *, res=None,
+                          bias=None, softcap=0.0, glu=0, act=0, **stage_kw):
+        """The same projection on the bf16 weights: a norm stage writes
+        bf16 rows (`stage_rows`) for the skinny bf16 MFMA GEMM, a RAW
+        input is read by the GEMM in place.  ``glu`` = I: the GLU is the
+        GEMM's epilogue, y[:, :I] of the [B, N = 2I] buffer."""
+        if stage_kw:
+            ho.stage_rows(x, xstride, self.bt_xs, B, K, **stage_kw)
+            x, xstride = self.bt_xs, K
+        ho.gemm_bf16_skinny(x, xstride, w, y, B, N, res=res,
+                            rstride=N if res is not None else 0, bias=bias,
+                            softcap=softcap, glu=glu, act=act,
+                            accbuf=self.b_gemm_acc)
+
+    def _batch_layers_fused(self, B: int, proj, sfx=("_q", "_s"),
+                            glu_epilogue=False):
         """Fused lockstep layer stack (fp8 / MXFP4): mirrors
         `_decode_layers`' 4-5 projections per layer over B rows, each one
         ``proj(wq, ws, x, xstride, y, K, N, res=, bias=, softcap=,
         **stage_kw)`` with the norm / embed gather / GLU as its staging
         op (`_proj_mx`, `_proj_skinny` or `_proj_skinny4`).  ``sfx``
         names the weight pair ``proj`` consumes: ("_q", "_s") the fp8
-        copy, ("_q4", "_e4") the MXFP4 one."""
+        copy, ("_q4", "_e4") the MXFP4 one, ("", "") the bf16 tensor
+        (twice).  ``glu_epilogue``: the wgu ``proj`` applies the GLU
+        itself (``glu=I, act=``, result in gu[:, :I]) and wdown reads
+        those rows RAW; otherwise the GLU is wdown's staging op."""
         qs, ss = sfx
         cfg = self.config
         eps = cfg.rms_norm_eps
@@ -1940,6 +1978,9 @@ class GPUModel:
         nhh = self.nh_l * self.hd
         glu = dict(stage=ho.STAGE_GLU, x2=gu[:, I:], x2stride=2 * I,
                    act=self.act)
+        gue = {}
+        if glu_epilogue:
+            glu, gue = {}, dict(glu=I, act=self.act)
 
         def norm2(g, g2):
             # h' = h + norm(x)*g persisted to the other h buffer, stage
@@ -1975,7 +2016,7 @@ class GPUModel:
                 proj(lw["wo" + qs], lw["wo" + ss], self.b_att, nhh, t1, nhh,
                      H)
                 proj(lw["wgu" + qs], lw["wgu" + ss], t1, H, gu, H, 2 * I,
-                     **norm2(lw["g_post"], lw["g_preffn"]))
+                     **norm2(lw["g_post"], lw["g_preffn"]), **gue)
                 h, hb = hb, h
                 proj(lw["wdown" + qs], lw["wdown" + ss], gu, 2 * I, t2, I,
                      H, **glu)
@@ -1983,7 +2024,7 @@ class GPUModel:
                 proj(lw["wo" + qs], lw["wo" + ss], self.b_att, nhh, h, nhh,
                      H, res=h)
                 proj(lw["wgu" + qs], lw["wgu" + ss], h, H, gu, H, 2 * I,
-                     stage=ho.STAGE_NORM, g=lw["g_post"], eps=eps)
+                     stage=ho.STAGE_NORM, g=lw["g_post"], eps=eps, **gue)
                 proj(lw["wdown" + qs], lw["wdown" + ss], gu, 2 * I, h, I,
                      H, res=h, **glu)
         if self.gemma:

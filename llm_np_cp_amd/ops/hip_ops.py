@@ -132,6 +132,20 @@ _SIGS = {
                                ctypes.c_int,
                                ctypes.c_float] + [ctypes.c_int] * 3 +
                               [ctypes.c_void_p],
+    "launch_stage_rows_bf16": [ctypes.c_void_p, ctypes.c_long,
+                               ctypes.c_void_p, ctypes.c_long] +
+                              [ctypes.c_void_p] * 3 +
+                              [ctypes.c_void_p, ctypes.c_long] +
+                              [ctypes.c_int] * 4 +
+                              [ctypes.c_float, ctypes.c_float,
+                               ctypes.c_void_p],
+    "launch_gemm_bf16_skinny": [ctypes.c_void_p, ctypes.c_long,
+                                ctypes.c_void_p, ctypes.c_void_p,
+                                ctypes.c_long, ctypes.c_void_p,
+                                ctypes.c_long, ctypes.c_void_p,
+                                ctypes.c_void_p, ctypes.c_long,
+                                ctypes.c_int, ctypes.c_float] +
+                               [ctypes.c_int] * 5 + [ctypes.c_void_p],
     "launch_gemv_fp8_mx": [ctypes.c_void_p] * 3 + [ctypes.c_long] +
                           [ctypes.c_void_p, ctypes.c_long] +
                           [ctypes.c_void_p] * 3 + [ctypes.c_long] +
@@ -1153,6 +1167,78 @@ def gemm_fp4_skinny(xq: torch.Tensor, sx: torch.Tensor, Wq4: torch.Tensor,
         ctypes.c_long(ystride), _ptr(res), ctypes.c_long(rstride),
         _ptr(bias), _ptr(accbuf), out_f32, ctypes.c_float(softcap),
         B, N, K, _stream()), "gemm_fp4_skinny")
+
+
+def stage_rows(x: torch.Tensor, xstride: int, xs: torch.Tensor, B: int,
+               K: int, stage: int = STAGE_NORM,
+               x2: torch.Tensor | None = None, x2stride: int = 0,
+               g: torch.Tensor | None = None,
+               g2: torch.Tensor | None = None,
+               hout: torch.Tensor | None = None, hstride: int = 0,
+               act: int = 0, eps: float = 1e-5, escale: float = 1.0):
+    """Per-sequence-row NORM / NORM2 / NORM_EMBED staging -> xs[B, K]
+    rounded to bf16 (feeds ``gemm_bf16_skinny``; RAW rows need no staging,
+    that GEMM reads them in place).  Strides in elements."""
+    if stage not in (STAGE_NORM, STAGE_NORM2, STAGE_NORM_EMBED):
+        raise ValueError(f"stage_rows: stage {stage} is not a norm stage")
+    if B < 1 or K % 16 != 0 or xs.numel() < B * K:
+        raise ValueError(f"stage_rows: B={B}, K={K}, xs {tuple(xs.shape)}")
+    _check(lib().launch_stage_rows_bf16(
+        _ptr(x), ctypes.c_long(xstride), _ptr(x2), ctypes.c_long(x2stride),
+        _ptr(g), _ptr(g2), _ptr(xs), _ptr(hout), ctypes.c_long(hstride),
+        K, B, stage, act, ctypes.c_float(eps), ctypes.c_float(escale),
+        _stream()), "stage_rows")
+
+
+def gemm_bf16_skinny(x: torch.Tensor, xstride: int, W: torch.Tensor,
+                     y: torch.Tensor, B: int, ystride: int,
+                     res: torch.Tensor | None = None, rstride: int = 0,
+                     bias: torch.Tensor | None = None, softcap: float = 0.0,
+                     glu: int = 0, act: int = 0,
+                     accbuf: torch.Tensor | None = None):
+    """Y[B<=16, N] = X @ W^T in bf16: one 16-row bf16 MFMA tile per wave,
+    W nt-streamed once, X rows read in place ``xstride`` elements apart.
+    Epilogue softcap -> bias -> res, bf16 or fp32 y.
+
+    glu = I: W = [gate rows; up rows] ([2I, K]) and y[b, n < I] =
+    act(bf16(g)) * bf16(u) — the bits of ``gemv(glu_pair=True)``; does
+    not compose with res / bias / softcap / fp32 output.
+
+    accbuf (fp32) enables the deterministic split-K: up to 8 slices of
+    B*N partial sums, as many as it has room for; too small for two
+    means no split."""
+    if W.dim() != 2 or not W.is_contiguous():
+        raise ValueError("gemm_bf16_skinny: weight rows must be contiguous")
+    N, K = W.shape
+    if not 1 <= B <= 16:
+        raise ValueError(f"gemm_bf16_skinny: B={B} outside 1..16")
+    if K % 32 != 0:
+        raise ValueError(f"gemm_bf16_skinny: K={K} is not a multiple of 32")
+    if xstride % 8 != 0 or x.numel() < (B - 1) * xstride + K:
+        raise ValueError(f"gemm_bf16_skinny: x has {x.numel()} elements, "
+                         f"B={B} rows of K={K} at stride {xstride} (a "
+                         f"multiple of 8) do not fit")
+    out_f32 = 1 if y.dtype == torch.float32 else 0
+    if glu:
+        bad = [n for n, on in (("res", res is not None),
+                               ("bias", bias is not None),
+                               ("softcap", softcap > 0.0),
+                               ("fp32 output", bool(out_f32))) if on]
+        if bad:
+            raise ValueError("gemm_bf16_skinny(glu=I) does not compose "
+                             "with " + ", ".join(bad))
+        if N % 2 or glu != N // 2:
+            raise ValueError(f"gemm_bf16_skinny: glu={glu} needs W with "
+                             f"2*glu rows, has {N}")
+    if y.numel() < (B - 1) * ystride + (glu or N):
+        raise ValueError("gemm_bf16_skinny: y smaller than B rows")
+    _check(lib().launch_gemm_bf16_skinny(
+        _ptr(x), ctypes.c_long(xstride), _ptr(W), _ptr(y),
+        ctypes.c_long(ystride), _ptr(res), ctypes.c_long(rstride),
+        _ptr(bias), _ptr(accbuf),
+        ctypes.c_long(0 if accbuf is None else accbuf.numel()), out_f32,
+        ctypes.c_float(softcap), glu, act, B, N, K, _stream()),
+        "gemm_bf16_skinny")
 
 
 def gemm_fp4w(X: torch.Tensor, Wq4: torch.Tensor, We4: torch.Tensor,
