@@ -5790,3 +5790,403 @@ extern "C" hipError_t launch_moe_scale_add(void* y, const void* x,
                      wstride, M, H);
   return hipGetLastError();
 }
+
+// ====================================================================
+// Token-grouped MoE expert GEMMs (prefill / lockstep rows, bf16).
+//
+// The dense E-loop above multiplies every row by every expert.  Here
+// the M*topk (row, expert) pairs are sorted by expert and ONE launch
+// per projection walks a device-built tile table:
+//   1. k_moe_group     stable counting sort of the pairs by expert ->
+//                      slot_row / slot_w / pair_slot / grp_off and the
+//                      (expert, first slot, rows) tile table for a tile
+//                      height TM; one block, LDS prefix sums, no atomics
+//   2. k_moe_gemm_glu_t<TM>   act[slot, I] = act(bf16(g)) * bf16(u),
+//                      A rows gathered from xn through slot_row
+//   3. k_moe_gemm_down_t<TM>  y[slot, H] (fp32) = act[slot] @ Wd[e]^T
+//   4. k_moe_combine   h[m] = bf16(h[m] + sum_j w * y[slot]) in
+//                      ascending slot (= expert) order, plain stores
+// Both GEMMs share one body: TM x 64 A tile and a 128-row B tile per
+// 64-deep K step, double-buffered in LDS by global_load_lds with the
+// XOR swizzle of k_gemm_bf16_t on the source address; 4 waves.  For the
+// gate/up GEMM the B tile is 64 gate rows + the matching 64 up rows, so
+// A is staged once for both and every lane holds g and u of the same
+// output element; for the down GEMM it is 128 consecutive rows.
+//   TM = 128: waves 2x2, 64 rows x 4 B fragments each (64 acc VGPRs)
+//   TM = 32:  waves 1x4, 32 rows x 2 B fragments each — an expert with a
+//             handful of rows streams its weights once per 32 slots
+// The grid is the routing-independent bound ceil(M*topk/TM) + E row
+// tiles; a block past the table's count exits (graph-capturable).
+// ====================================================================
+
+#define MOE_TMS 32
+#define MOE_TMP 128
+#define MOE_MAX_PAIRS 65535
+
+// scalar fp32 only, as the skinny kernels above
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MOE_KERNEL(nthr) \
+  __global__ void __launch_bounds__(nthr) \
+      __attribute__((target("no-packed-fp32-ops")))
+#else
+#define MOE_KERNEL(nthr) __global__ void __launch_bounds__(nthr)
+#endif
+
+// bad device data must not index outside the LDS histogram
+DEVINL int moe_expert(const int* __restrict__ idx, int p, int E) {
+  const int e = idx[p];
+  return e < 0 ? 0 : (e >= E ? E - 1 : e);
+}
+
+// tiles[0] = tile count, then (expert, first slot, rows) per tile.
+// Thread t owns the contiguous pairs [t*chunk, (t+1)*chunk): per-thread
+// histograms -> per-expert scan over the 256 threads -> scan over the
+// experts; a pair's slot is group offset + threads before + own pairs
+// before, a function of idx alone.  Counts are u16: n <= 65535.
+extern "C" MOE_KERNEL(256)
+k_moe_group(const int* __restrict__ idx, const float* __restrict__ w,
+            int n, int topk, int E, int TM, int* __restrict__ slot_row,
+            float* __restrict__ slot_w, int* __restrict__ pair_slot,
+            int* __restrict__ grp_off, int* __restrict__ tiles) {
+  __shared__ u16 cnt[64 * 256];
+  __shared__ int goff[64];
+  const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+  const int chunk = (n + 255) / 256;
+  const int p0 = t * chunk;
+  const int p1 = p0 + chunk < n ? p0 + chunk : n;
+  for (int e = 0; e < E; e++) cnt[e * 256 + t] = 0;
+  for (int p = p0; p < p1; p++) cnt[moe_expert(idx, p, E) * 256 + t]++;
+  __syncthreads();
+  for (int e = wave; e < E; e += 4) {  // exclusive scan over threads
+    u16* c = cnt + e * 256 + lane * 4;
+    const int a0 = c[0], a1 = c[1], a2 = c[2], a3 = c[3];
+    const int s = a0 + a1 + a2 + a3;
+    int inc = s;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      int v = __shfl_up(inc, d);
+      if (lane >= d) inc += v;
+    }
+    const int ex = inc - s;
+    c[0] = (u16)ex;
+    c[1] = (u16)(ex + a0);
+    c[2] = (u16)(ex + a0 + a1);
+    c[3] = (u16)(ex + a0 + a1 + a2);
+    if (lane == 63) goff[e] = inc;  // the expert's pair count
+  }
+  __syncthreads();
+  if (wave == 0) {  // lane e: group offset and first tile of expert e
+    const int c = lane < E ? goff[lane] : 0;
+    const int nt = (c + TM - 1) / TM;
+    int io = c, it = nt;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      int v = __shfl_up(io, d), u = __shfl_up(it, d);
+      if (lane >= d) { io += v; it += u; }
+    }
+    const int off = io - c, tb = it - nt;
+    if (lane < E) {
+      goff[lane] = off;
+      grp_off[lane] = off;
+    }
+    if (lane == E - 1) {
+      grp_off[E] = io;
+      tiles[0] = it;
+    }
+    for (int k = 0; k < nt; k++) {
+      int* tt = tiles + 1 + 3 * (tb + k);
+      tt[0] = lane;
+      tt[1] = off + k * TM;
+      tt[2] = c - k * TM < TM ? c - k * TM : TM;
+    }
+  }
+  __syncthreads();
+  for (int p = p0; p < p1; p++) {
+    const int e = moe_expert(idx, p, E);
+    const int s = goff[e] + cnt[e * 256 + t]++;
+    slot_row[s] = p / topk;
+    slot_w[s] = w[p];
+    pair_slot[p] = s;
+  }
+}
+
+extern "C" hipError_t launch_moe_group(const void* idx, const void* w, int M,
+                                       int topk, int E, int tm,
+                                       void* slot_row, void* slot_w,
+                                       void* pair_slot, void* grp_off,
+                                       void* tiles, hipStream_t stream) {
+  if (E < 1 || E > 64 || topk < 1 || topk > 8 || M < 1 ||
+      (long)M * topk > MOE_MAX_PAIRS || (tm != MOE_TMS && tm != MOE_TMP))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_moe_group, dim3(1), dim3(256), 0, stream,
+                     (const int*)idx, (const float*)w, M * topk, topk, E, tm,
+                     (int*)slot_row, (float*)slot_w, (int*)pair_slot,
+                     (int*)grp_off, (int*)tiles);
+  return hipGetLastError();
+}
+
+// One tile of a grouped GEMM: out[first + r, n0 + c] for r < rows.
+//   GLU:  A row r = X[slot_row[first + r]], B = [gate n0..+64; up n0..+64]
+//         of the expert's [2N, K] block, outb = glu_act(g, u) (bf16)
+//   else: A row r = X[first + r], B = rows n0..+128 of the expert's
+//         [N, K] block, outf = fp32 accumulator
+// Rows past `rows` and B rows past N are clamped to a valid source and
+// never stored.
+template <int TM, bool GLU>
+DEVINL void moe_gemm_tile(u16* As, u16* Bs, const u16* __restrict__ X,
+                          const int* __restrict__ slot_row,
+                          const u16* __restrict__ Wall,
+                          const int* __restrict__ tiles,
+                          u16* __restrict__ outb, float* __restrict__ outf,
+                          int N, int K, int act) {
+  constexpr int WR = TM >= 128 ? 2 : 1, WC = 4 / WR;  // wave grid
+  constexpr int SUBM = TM / WR;       // rows per wave
+  constexpr int FM = SUBM / 16;       // A fragments per wave
+  constexpr int FB = 128 / (16 * WC);  // B fragments per wave
+  constexpr int FN = FB / 2;          // GLU: gate (and up) fragments
+  constexpr int TN = GLU ? 64 : 128;  // output columns per block
+  constexpr int AI = TM / 32;         // A staging calls per wave
+  const int ti = blockIdx.x;
+  if (ti >= tiles[0]) return;
+  const int e = tiles[1 + 3 * ti], first = tiles[2 + 3 * ti];
+  const int rows = tiles[3 + 3 * ti];
+  const int n0 = blockIdx.y * TN;
+  const u16* W = Wall + (size_t)e * (GLU ? 2 : 1) * N * K;
+
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int wrow = wave / WC, wcol = wave % WC;
+  const int g_r = lane >> 3, g_s = lane & 7;
+
+  // per-lane source rows are the same for every K step: look them up
+  // (A: through the sort) once, swizzled col-slot folded in
+  const u16* ap[AI];
+  const u16* bp[4];
+#pragma unroll
+  for (int i = 0; i < AI; i++) {
+    int r = wave * (TM / 4) + i * 8 + g_r;
+    int s = first + (r < rows ? r : rows - 1);
+    int src = GLU ? slot_row[s] : s;
+    ap[i] = X + (size_t)src * K + (g_s ^ (r & 7)) * 8;
+  }
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    int r = wave * 32 + i * 8 + g_r;  // B tile row 0..127
+    int c = n0 + (GLU ? (r & 63) : r);
+    c = c < N ? c : N - 1;
+    int wr = GLU ? (r >> 6) * N + c : c;
+    bp[i] = W + (size_t)wr * K + (g_s ^ (r & 7)) * 8;
+  }
+  auto stage = [&](int buf, int kt) {
+    const int k0 = kt * 64;
+#pragma unroll
+    for (int i = 0; i < AI; i++)
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) uint32_t*)(ap[i] + k0),
+          (__attribute__((address_space(3))) uint32_t*)(
+              As + buf * (TM * 64) + (wave * (TM / 4) + i * 8) * 64),
+          16, 0, 0);
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) uint32_t*)(bp[i] + k0),
+          (__attribute__((address_space(3))) uint32_t*)(
+              Bs + buf * (128 * 64) + (wave * 32 + i * 8) * 64),
+          16, 0, 0);
+  };
+
+  f4v acc[FM][FB];
+#pragma unroll
+  for (int i = 0; i < FM; i++)
+#pragma unroll
+    for (int j = 0; j < FB; j++) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+
+  const int nt = K / 64;
+  stage(0, 0);
+  __syncthreads();
+  const int fr = lane & 15, fk = lane >> 4;
+  int cur = 0;
+  for (int t = 0; t < nt; t++) {
+    if (t + 1 < nt) stage(cur ^ 1, t + 1);
+    const u16* Ac = As + cur * (TM * 64);
+    const u16* Bc = Bs + cur * (128 * 64);
+#pragma unroll
+    for (int sl = 0; sl < 2; sl++) {
+      bf16x8 a[FM], b[FB];
+#pragma unroll
+      for (int i = 0; i < FM; i++) {
+        int ra = wrow * SUBM + i * 16 + fr;
+        a[i] = *(const bf16x8*)(Ac + ra * 64 +
+                                (((sl * 4 + fk) ^ (ra & 7)) * 8));
+      }
+#pragma unroll
+      for (int j = 0; j < FB; j++) {
+        int rb = GLU ? (j / FN) * 64 + wcol * (FN * 16) + (j % FN) * 16 + fr
+                     : wcol * (FB * 16) + j * 16 + fr;
+        b[j] = *(const bf16x8*)(Bc + rb * 64 +
+                                (((sl * 4 + fk) ^ (rb & 7)) * 8));
+      }
+#pragma unroll
+      for (int i = 0; i < FM; i++)
+#pragma unroll
+        for (int j = 0; j < FB; j++)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              a[i], b[j], acc[i][j], 0, 0, 0);
+    }
+    __syncthreads();  // drains the DMA of the next tile; read fence
+    cur ^= 1;
+  }
+
+  // C layout: col = lane & 15, row = (lane >> 4) * 4 + reg
+  const int cc = lane & 15, cr = (lane >> 4) * 4;
+#pragma unroll
+  for (int i = 0; i < FM; i++) {
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int row = wrow * SUBM + i * 16 + cr + r;
+      if (row >= rows) continue;
+      const size_t o = (size_t)(first + row) * N;
+      if (GLU) {
+#pragma unroll
+        for (int j = 0; j < FN; j++) {
+          int col = n0 + wcol * (FN * 16) + j * 16 + cc;
+          if (col < N)
+            outb[o + col] = glu_act(b2f(f2b(acc[i][j][r])),
+                                    b2f(f2b(acc[i][j + FN][r])), act);
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < FB; j++) {
+          int col = n0 + wcol * (FB * 16) + j * 16 + cc;
+          if (col < N) outf[o + col] = acc[i][j][r];
+        }
+      }
+    }
+  }
+}
+
+template <int TM>
+MOE_KERNEL(256)
+k_moe_gemm_glu_t(const u16* __restrict__ xn, const int* __restrict__ slot_row,
+                 const u16* __restrict__ wgu_all,
+                 const int* __restrict__ tiles, u16* __restrict__ actb,
+                 int I, int H, int act) {
+  __shared__ u16 As[2 * TM * 64];
+  __shared__ u16 Bs[2 * 128 * 64];
+  moe_gemm_tile<TM, true>(As, Bs, xn, slot_row, wgu_all, tiles, actb,
+                          nullptr, I, H, act);
+}
+
+template <int TM>
+MOE_KERNEL(256)
+k_moe_gemm_down_t(const u16* __restrict__ actb,
+                  const u16* __restrict__ wdown_all,
+                  const int* __restrict__ tiles, float* __restrict__ y,
+                  int H, int I) {
+  __shared__ u16 As[2 * TM * 64];
+  __shared__ u16 Bs[2 * 128 * 64];
+  moe_gemm_tile<TM, false>(As, Bs, actb, nullptr, wdown_all, tiles, nullptr,
+                           y, H, I, 0);
+}
+
+static bool moe_gemm_args_ok(int M, int topk, int E, int H, int I, int tm) {
+  return E >= 1 && E <= 64 && topk >= 1 && topk <= 8 && M >= 1 &&
+         (long)M * topk <= MOE_MAX_PAIRS && H >= 64 && I >= 64 &&
+         (tm == MOE_TMS || tm == MOE_TMP);
+}
+
+extern "C" hipError_t launch_moe_gemm_glu(const void* xn,
+                                          const void* slot_row,
+                                          const void* wgu_all,
+                                          const void* tiles, void* actb,
+                                          int M, int topk, int E, int H,
+                                          int I, int act, int tm,
+                                          hipStream_t stream) {
+  if (!moe_gemm_args_ok(M, topk, E, H, I, tm) || H % 64 != 0)
+    return hipErrorInvalidValue;
+  dim3 grid((M * topk + tm - 1) / tm + E, (I + 63) / 64);
+#define MOE_GLU_LAUNCH(TMV)                                               \
+  hipLaunchKernelGGL((k_moe_gemm_glu_t<TMV>), grid, dim3(256), 0, stream, \
+                     (const u16*)xn, (const int*)slot_row,                \
+                     (const u16*)wgu_all, (const int*)tiles, (u16*)actb,  \
+                     I, H, act)
+  if (tm == MOE_TMP) MOE_GLU_LAUNCH(MOE_TMP); else MOE_GLU_LAUNCH(MOE_TMS);
+#undef MOE_GLU_LAUNCH
+  return hipGetLastError();
+}
+
+extern "C" hipError_t launch_moe_gemm_down(const void* actb,
+                                           const void* wdown_all,
+                                           const void* tiles, void* y, int M,
+                                           int topk, int E, int H, int I,
+                                           int tm, hipStream_t stream) {
+  if (!moe_gemm_args_ok(M, topk, E, H, I, tm) || I % 64 != 0)
+    return hipErrorInvalidValue;
+  dim3 grid((M * topk + tm - 1) / tm + E, (H + 127) / 128);
+#define MOE_DOWN_LAUNCH(TMV)                                               \
+  hipLaunchKernelGGL((k_moe_gemm_down_t<TMV>), grid, dim3(256), 0, stream, \
+                     (const u16*)actb, (const u16*)wdown_all,              \
+                     (const int*)tiles, (float*)y, H, I)
+  if (tm == MOE_TMP) MOE_DOWN_LAUNCH(MOE_TMP); else MOE_DOWN_LAUNCH(MOE_TMS);
+#undef MOE_DOWN_LAUNCH
+  return hipGetLastError();
+}
+
+// h[m, :] = bf16(h[m, :] + sum_j slot_w[s_j] * y[s_j, :]), s_j the row's
+// slots in ascending order (= ascending expert), fp32 throughout.  One
+// block per row: nobody else writes that row, so plain stores.
+extern "C" MOE_KERNEL(256)
+k_moe_combine(u16* __restrict__ h, const float* __restrict__ y,
+              const int* __restrict__ pair_slot,
+              const float* __restrict__ slot_w, int H, int topk) {
+  __shared__ int so[8];
+  __shared__ float sw[8];
+  const int m = blockIdx.x;
+  if (threadIdx.x == 0) {
+    const int* ps = pair_slot + (size_t)m * topk;
+    int prev = -1;
+    for (int t = 0; t < topk; t++) {
+      int best = 0x7fffffff;
+      for (int j = 0; j < topk; j++) {
+        int s = ps[j];
+        if (s > prev && s < best) best = s;
+      }
+      so[t] = best;
+      sw[t] = slot_w[best];
+      prev = best;
+    }
+  }
+  __syncthreads();
+  u16* hr = h + (size_t)m * H;
+  for (int c = threadIdx.x * 4; c < H; c += 256 * 4) {
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    for (int t = 0; t < topk; t++) {
+      const f4v v = *(const f4v*)(y + (size_t)so[t] * H + c);
+      const float wv = sw[t];
+      s0 += wv * v[0];
+      s1 += wv * v[1];
+      s2 += wv * v[2];
+      s3 += wv * v[3];
+    }
+    const uint2 hv = *(const uint2*)(hr + c);
+    const u16* hp = (const u16*)&hv;
+    u16 o[4];
+    o[0] = f2b(b2f(hp[0]) + s0);
+    o[1] = f2b(b2f(hp[1]) + s1);
+    o[2] = f2b(b2f(hp[2]) + s2);
+    o[3] = f2b(b2f(hp[3]) + s3);
+    *(uint2*)(hr + c) = *(const uint2*)o;
+  }
+}
+
+extern "C" hipError_t launch_moe_combine(void* h, const void* y,
+                                         const void* pair_slot,
+                                         const void* slot_w, int M, int H,
+                                         int topk, hipStream_t stream) {
+  if (M < 1 || H < 4 || H % 4 != 0 || topk < 1 || topk > 8)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_moe_combine, dim3(M), dim3(256), 0, stream, (u16*)h,
+                     (const float*)y, (const int*)pair_slot,
+                     (const float*)slot_w, H, topk);
+  return hipGetLastError();
+}

@@ -74,7 +74,8 @@ class GPUModel:
                  seed: int = 0, force_tp_path: bool = False,
                  kv_dtype: str = "bf16", max_batch: int = 1,
                  batch_fp4: Optional[bool] = None,
-                 batch_skinny: Optional[bool] = None):
+                 batch_skinny: Optional[bool] = None,
+                 moe_grouped: Optional[bool] = None):
         """``max_seq=None`` sizes the KV pool from FREE HBM after the
         weights land (288 GB per MI355X — SURVEY §5 long-context), capped
         at config.max_position_embeddings.  ``max_batch>1`` allocates
@@ -87,7 +88,11 @@ class GPUModel:
         env LLM_BATCH_SKINNY, default off) runs the lockstep steps of a
         bf16, ``max_batch>1``, single-GPU, non-MoE engine up to B = 16
         on the bf16 skinny MFMA GEMM (`_proj_skinny_bf16`); ignored for
-        every other engine."""
+        every other engine.  ``moe_grouped`` (None = env LLM_MOE_GROUPED,
+        default off) runs the prefill / lockstep-row MLP of a bf16,
+        single-GPU MoE engine on the token-grouped expert GEMMs
+        (`_moe_mlp_rows_grouped`) instead of the dense per-expert loop;
+        ignored for every other engine (fp8 experts keep the loop)."""
         if not torch.cuda.is_available():
             raise RuntimeError("GPUModel requires a GPU (MI355X)")
         self.config = config
@@ -122,6 +127,12 @@ class GPUModel:
                 not in ("", "0")
         self.batch_skinny = bool(batch_skinny and dtype == "bf16"
                                  and max_batch > 1 and not config.is_moe)
+        if moe_grouped is None:
+            import os as _os
+            moe_grouped = _os.environ.get("LLM_MOE_GROUPED", "0").strip() \
+                not in ("", "0")
+        self.moe_grouped = bool(moe_grouped and dtype == "bf16"
+                                and config.is_moe)
         if kv_dtype not in ("bf16", "fp8"):
             raise ValueError(f"unsupported kv_dtype {kv_dtype!r}")
         self.kv_dtype = kv_dtype
@@ -138,6 +149,7 @@ class GPUModel:
                 raise ValueError("MoE is a llama-family (Mixtral) feature")
         self.rank, self.world = tpu.init_distributed()
         self.batch_skinny = self.batch_skinny and self.world == 1
+        self.moe_grouped = self.moe_grouped and self.world == 1
         # exercise the TP code path on 1 GPU (collectives no-op at
         # world=1, partial sums are then exact) — used by tests
         self.tp_branch = self.world > 1 or force_tp_path
@@ -537,6 +549,29 @@ class GPUModel:
                                      device=dev)
             self.moe_dense = torch.zeros(PC * E, dtype=torch.float32,
                                          device=dev)
+            if self.moe_grouped:
+                # sort outputs, tile table (sized for the short tile: the
+                # larger bound) and the per-slot activation / fp32 down
+                # buffers of the grouped expert GEMMs
+                NP = PC * self.topk
+                if NP > ho.MOE_MAX_PAIRS:
+                    raise ValueError(
+                        f"moe_grouped: prefill_chunk * topk = {NP} pairs "
+                        f"> {ho.MOE_MAX_PAIRS}")
+                self.moe_slot_row = torch.zeros(NP, dtype=torch.int32,
+                                                device=dev)
+                self.moe_slot_w = torch.zeros(NP, dtype=torch.float32,
+                                              device=dev)
+                self.moe_pair_slot = torch.zeros(NP, dtype=torch.int32,
+                                                 device=dev)
+                self.moe_grp_off = torch.zeros(E + 1, dtype=torch.int32,
+                                               device=dev)
+                self.moe_tiles = torch.zeros(
+                    1 + 3 * ho.moe_max_tiles(PC, self.topk, E, ho.MOE_TMS),
+                    dtype=torch.int32, device=dev)
+                self.moe_act = torch.zeros(NP, I, **bf)
+                self.moe_y = torch.zeros(NP, H, dtype=torch.float32,
+                                         device=dev)
         self.b_hb = torch.zeros(H, **bf)   # gemma residual ping-pong
         self.b_t2 = torch.zeros(H, **bf)   # gemma ffn-out delta
         self.b_gu = torch.zeros(2 * I, **bf)
@@ -812,6 +847,8 @@ class GPUModel:
         unrouted).  Work is E/topk x the routed minimum — prefill is
         compute-rich and this keeps the MFMA GEMM path; decode uses the
         expert-indexed GEMVs instead (`_decode_step`)."""
+        if self.moe_grouped:
+            return self._moe_mlp_rows_grouped(lw, M)
         cfg = self.config
         E, I, H = cfg.num_local_experts, self.inter_l, self.H
         eps = cfg.rms_norm_eps
@@ -848,6 +885,28 @@ class GPUModel:
                 ho.gemm(gate[:M], lw["wdown_all"][d_lo:d_hi], t1[:M],
                         accbuf=self.b_gemm_acc)
             ho.moe_scale_add(self.b_h, t1, self.moe_dense[e:], E, M, H)
+
+    def _moe_mlp_rows_grouped(self, lw, M: int):
+        """The same MLP on the routed pairs only: route -> sort the
+        (row, expert) pairs by expert on the device -> ONE gate+up GEMM
+        launch over all experts (A gathered through the sort, GLU in the
+        epilogue) -> ONE down GEMM launch (fp32 per slot) -> combine into
+        h in ascending expert order.  5 launches per layer, no host
+        read; the tile height follows M * topk / E (`ho.moe_tile_rows`)."""
+        E, k = self.config.num_local_experts, self.topk
+        ho.moe_route(self.b_h, lw["g_post"], lw["wg"], M, k, self.moe_idx,
+                     self.moe_w, eps=self.config.rms_norm_eps)
+        tm = ho.moe_group(self.moe_idx, self.moe_w, M, k, E,
+                          self.moe_slot_row, self.moe_slot_w,
+                          self.moe_pair_slot, self.moe_grp_off,
+                          self.moe_tiles)
+        ho.moe_gemm_glu(self.b_xn, self.moe_slot_row, lw["wgu_all"],
+                        self.moe_tiles, self.moe_act, M, k, tm,
+                        act=self.act)
+        ho.moe_gemm_down(self.moe_act, lw["wdown_all"], self.moe_tiles,
+                         self.moe_y, M, k, tm)
+        ho.moe_combine(self.b_h, self.moe_y, self.moe_pair_slot,
+                       self.moe_slot_w, M, k)
 
     def _lm_head_last(self, M: int):
         """Final norm + lm_head on the last row -> self.b_logits (f32, V);

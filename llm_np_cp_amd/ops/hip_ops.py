@@ -163,6 +163,14 @@ _SIGS = {
     "launch_moe_scale_add": [ctypes.c_void_p] * 3 +
                             [ctypes.c_long, ctypes.c_int, ctypes.c_int,
                              ctypes.c_void_p],
+    "launch_moe_group": [ctypes.c_void_p] * 2 + [ctypes.c_int] * 4 +
+                        [ctypes.c_void_p] * 6,
+    "launch_moe_gemm_glu": [ctypes.c_void_p] * 5 + [ctypes.c_int] * 7 +
+                           [ctypes.c_void_p],
+    "launch_moe_gemm_down": [ctypes.c_void_p] * 4 + [ctypes.c_int] * 6 +
+                            [ctypes.c_void_p],
+    "launch_moe_combine": [ctypes.c_void_p] * 4 + [ctypes.c_int] * 3 +
+                          [ctypes.c_void_p],
     # one-shot xGMI collectives (csrc/xgmi_comm.hip)
     "launch_xgmi_coll": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                          ctypes.c_int, ctypes.c_int, ctypes.c_long,
@@ -1374,3 +1382,161 @@ def moe_scale_add(y: torch.Tensor, x: torch.Tensor, w: torch.Tensor,
     _check(lib().launch_moe_scale_add(
         _ptr(y), _ptr(x), _ptr(w), ctypes.c_long(wstride), M, H,
         _stream()), "moe_scale_add")
+
+
+# ----------------------------------------------------------------------
+# token-grouped MoE expert GEMMs (prefill / lockstep rows, bf16)
+# ----------------------------------------------------------------------
+
+MOE_TMS, MOE_TMP = 32, 128     # short / prefill tile heights
+MOE_MAX_PAIRS = 65535          # k_moe_group counts in u16
+
+
+def moe_tile_rows(M: int, topk: int, E: int) -> int:
+    """Tile height of the grouped GEMMs: the 128-row prefill tile once
+    the average expert sees at least half of one (M*topk/E >= 64), the
+    32-row tile below that — a handful of rows per expert makes the
+    launch a weight stream, and short tiles waste fewer MFMA rows."""
+    return MOE_TMP if M * topk >= 64 * E else MOE_TMS
+
+
+def moe_max_tiles(M: int, topk: int, E: int, tm: int) -> int:
+    """Routing-independent bound on the tile count (the GEMMs' grid.x)."""
+    return (M * topk + tm - 1) // tm + E
+
+
+def _moe_dims(name, M, topk, E, tm):
+    if not 1 <= E <= 64:
+        raise ValueError(f"{name}: E={E} outside 1..64")
+    if not 1 <= topk <= min(8, E):
+        raise ValueError(f"{name}: topk={topk} outside 1..min(8, E)")
+    if M < 1 or M * topk > MOE_MAX_PAIRS:
+        raise ValueError(f"{name}: M={M} rows x topk={topk} outside "
+                         f"1..{MOE_MAX_PAIRS} pairs")
+    if tm not in (MOE_TMS, MOE_TMP):
+        raise ValueError(f"{name}: tile height {tm} is not {MOE_TMS} or "
+                         f"{MOE_TMP}")
+
+
+def _moe_buf(name, what, t, dtype, n):
+    if (t.dtype != dtype or not t.is_cuda or not t.is_contiguous()
+            or t.numel() < n):
+        raise ValueError(f"{name}: {what} must be a contiguous {dtype} GPU "
+                         f"tensor of >= {n} elements")
+
+
+def moe_group(idx: torch.Tensor, w: torch.Tensor, M: int, topk: int, E: int,
+              slot_row: torch.Tensor, slot_w: torch.Tensor,
+              pair_slot: torch.Tensor, grp_off: torch.Tensor,
+              tiles: torch.Tensor, tm: int | None = None) -> int:
+    """Stable counting sort of the M*topk (row, expert) pairs of
+    ``moe_route`` by expert, on the device, and the tile table of the
+    grouped GEMMs for tile height ``tm`` (None = ``moe_tile_rows``;
+    returned).  slot_row / slot_w [M*topk]: source row and router weight
+    per slot; pair_slot [M*topk]: slot of pair m*topk+j; grp_off [E+1];
+    tiles [1 + 3*moe_max_tiles]: count, then (expert, first slot, rows)
+    per tile.  The layout is a function of idx alone."""
+    if tm is None:
+        tm = moe_tile_rows(M, topk, E)
+    _moe_dims("moe_group", M, topk, E, tm)
+    n = M * topk
+    _moe_buf("moe_group", "idx", idx, torch.int32, n)
+    _moe_buf("moe_group", "w", w, torch.float32, n)
+    _moe_buf("moe_group", "slot_row", slot_row, torch.int32, n)
+    _moe_buf("moe_group", "slot_w", slot_w, torch.float32, n)
+    _moe_buf("moe_group", "pair_slot", pair_slot, torch.int32, n)
+    _moe_buf("moe_group", "grp_off", grp_off, torch.int32, E + 1)
+    _moe_buf("moe_group", "tiles", tiles, torch.int32,
+             1 + 3 * moe_max_tiles(M, topk, E, tm))
+    _check(lib().launch_moe_group(
+        _ptr(idx), _ptr(w), M, topk, E, tm, _ptr(slot_row), _ptr(slot_w),
+        _ptr(pair_slot), _ptr(grp_off), _ptr(tiles), _stream()), "moe_group")
+    return tm
+
+
+def moe_gemm_glu(xn: torch.Tensor, slot_row: torch.Tensor,
+                 wgu_all: torch.Tensor, tiles: torch.Tensor,
+                 act_out: torch.Tensor, M: int, topk: int, tm: int,
+                 act: int = 0):
+    """Grouped gate+up GEMM with the GLU epilogue, one launch for all
+    experts: act_out[s, :I] = act(bf16(g)) * bf16(u) for every slot s of
+    ``moe_group`` (same ``tm``), g/u = xn[slot_row[s]] @ the gate / up
+    rows of that slot's expert.  xn [>= M, H] bf16; wgu_all [E*2I, H]
+    bf16, per expert [gate; up]; act_out >= M*topk*I bf16."""
+    if (xn.dim() != 2 or wgu_all.dim() != 2 or not xn.is_contiguous()
+            or not wgu_all.is_contiguous()
+            or xn.dtype != torch.bfloat16 or wgu_all.dtype != torch.bfloat16):
+        raise ValueError("moe_gemm_glu: xn and wgu_all must be contiguous "
+                         "2-D bf16")
+    H = xn.shape[1]
+    if H % 64 != 0 or wgu_all.shape[1] != H:
+        raise ValueError(f"moe_gemm_glu: K={H} must be a multiple of 64 and "
+                         f"match wgu_all {tuple(wgu_all.shape)}")
+    if xn.shape[0] < M:
+        raise ValueError(f"moe_gemm_glu: xn has {xn.shape[0]} rows < M={M}")
+    if act_out.dim() != 2:
+        raise ValueError("moe_gemm_glu: act_out must be [slots, I]")
+    I = act_out.shape[1]
+    if I < 64 or wgu_all.shape[0] % (2 * I) != 0:
+        raise ValueError(f"moe_gemm_glu: wgu_all rows {wgu_all.shape[0]} are "
+                         f"not E blocks of 2*I, I={I} >= 64")
+    E = wgu_all.shape[0] // (2 * I)
+    _moe_dims("moe_gemm_glu", M, topk, E, tm)
+    _moe_buf("moe_gemm_glu", "slot_row", slot_row, torch.int32, M * topk)
+    _moe_buf("moe_gemm_glu", "tiles", tiles, torch.int32,
+             1 + 3 * moe_max_tiles(M, topk, E, tm))
+    _moe_buf("moe_gemm_glu", "act_out", act_out, torch.bfloat16,
+             M * topk * I)
+    _check(lib().launch_moe_gemm_glu(
+        _ptr(xn), _ptr(slot_row), _ptr(wgu_all), _ptr(tiles), _ptr(act_out),
+        M, topk, E, H, I, act, tm, _stream()), "moe_gemm_glu")
+
+
+def moe_gemm_down(act_in: torch.Tensor, wdown_all: torch.Tensor,
+                  tiles: torch.Tensor, y: torch.Tensor, M: int, topk: int,
+                  tm: int):
+    """Grouped down GEMM: y[s, :H] (fp32) = act_in[s, :I] @ Wd[e(s)]^T
+    for every slot s, one launch.  act_in [>= M*topk, I] bf16 in slot
+    order; wdown_all [E*H, I] bf16; y [>= M*topk, H] fp32."""
+    if (act_in.dim() != 2 or wdown_all.dim() != 2 or y.dim() != 2
+            or not act_in.is_contiguous() or not wdown_all.is_contiguous()
+            or act_in.dtype != torch.bfloat16
+            or wdown_all.dtype != torch.bfloat16):
+        raise ValueError("moe_gemm_down: act_in and wdown_all must be "
+                         "contiguous 2-D bf16, y 2-D")
+    I, H = act_in.shape[1], y.shape[1]
+    if I % 64 != 0 or wdown_all.shape[1] != I:
+        raise ValueError(f"moe_gemm_down: K={I} must be a multiple of 64 and "
+                         f"match wdown_all {tuple(wdown_all.shape)}")
+    if H < 64 or H % 4 != 0 or wdown_all.shape[0] % H != 0:
+        raise ValueError(f"moe_gemm_down: wdown_all rows "
+                         f"{wdown_all.shape[0]} are not E blocks of H={H}")
+    E = wdown_all.shape[0] // H
+    _moe_dims("moe_gemm_down", M, topk, E, tm)
+    _moe_buf("moe_gemm_down", "act_in", act_in, torch.bfloat16, M * topk * I)
+    _moe_buf("moe_gemm_down", "tiles", tiles, torch.int32,
+             1 + 3 * moe_max_tiles(M, topk, E, tm))
+    _moe_buf("moe_gemm_down", "y", y, torch.float32, M * topk * H)
+    _check(lib().launch_moe_gemm_down(
+        _ptr(act_in), _ptr(wdown_all), _ptr(tiles), _ptr(y), M, topk, E, H,
+        I, tm, _stream()), "moe_gemm_down")
+
+
+def moe_combine(h: torch.Tensor, y: torch.Tensor, pair_slot: torch.Tensor,
+                slot_w: torch.Tensor, M: int, topk: int):
+    """h[m] = bf16(h[m] + sum_j slot_w[s] * y[s]) over the row's slots s
+    in ascending (= expert) order, fp32 sums; rows >= M untouched.
+    h [>= M, H] bf16; y [>= M*topk, H] fp32."""
+    if h.dim() != 2 or y.dim() != 2 or h.shape[1] != y.shape[1]:
+        raise ValueError("moe_combine: h [rows, H] and y [slots, H]")
+    H = h.shape[1]
+    if H % 4 != 0 or not 1 <= topk <= 8 or M < 1:
+        raise ValueError(f"moe_combine: H={H} (multiple of 4), topk={topk} "
+                         f"(1..8), M={M}")
+    _moe_buf("moe_combine", "h", h, torch.bfloat16, M * H)
+    _moe_buf("moe_combine", "y", y, torch.float32, M * topk * H)
+    _moe_buf("moe_combine", "pair_slot", pair_slot, torch.int32, M * topk)
+    _moe_buf("moe_combine", "slot_w", slot_w, torch.float32, M * topk)
+    _check(lib().launch_moe_combine(
+        _ptr(h), _ptr(y), _ptr(pair_slot), _ptr(slot_w), M, H, topk,
+        _stream()), "moe_combine")
