@@ -6132,6 +6132,272 @@ extern "C" hipError_t launch_moe_gemm_down(const void* actb,
   return hipGetLastError();
 }
 
+// ====================================================================
+// The grouped GEMMs on the engine's e4m3 experts: both MFMA operands
+// fp8 (v_mfma_f32_16x16x32_fp8_fp8), per-row scales in the epilogue.
+// Same sort, tile table, grid and wave grids as the bf16 pair; the tile
+// body is its own because the bytes mean something else:
+//   - one K step is 128 elements = a 128-byte LDS row = eight 16-byte
+//     chunks, staged by the same global_load_lds / XOR-swizzle scheme
+//     (LDS chunk c of row r holds source chunk c ^ (r & 7)); TM x 128 B
+//     of A and 128 x 128 B of B per buffer, two buffers: 64 KB / 40 KB.
+//   - the MFMA wants 8 bytes per lane per operand.  For each 64-byte
+//     half hf of the row, lane (fr = lane & 15, fk = lane >> 4) reads
+//     the whole 16-byte chunk hf * 4 + fk of row fr with one
+//     ds_read_b128 and feeds its low 8 bytes to one MFMA and its high 8
+//     bytes to the next.  The MFMA's k index fk * 8 + b then stands for
+//     element hf * 64 + fk * 16 + {0, 8} + b: a permutation of K that A
+//     and B share, so every product x[k] * w[k] is formed exactly once.
+//     LDS reads per step equal the bf16 body's, at twice the K.
+//   - K % 64 == 0 (tiny-mixtral has H = 64), so the last step may hold
+//     only 64 valid bytes: source chunks 0..3.  The lanes whose swizzled
+//     source chunk is 4..7 would read past the row (for the tensor's
+//     last row: past the allocation), so in that step they step back 64
+//     bytes to chunk & 3 of the same row, which lands in LDS chunks that
+//     nobody reads: the second half's MFMAs are skipped, uniformly for
+//     the block.  The valid chunks sit where a full step puts them.
+//     Clamping the address keeps the staging call unpredicated, so all
+//     64 lanes take part in the DMA's contiguous LDS write.
+//   glu:  g = acc_g * sx[slot_row[s]] * ws[e*2I + col], u likewise with
+//         the up row's scale, each rounded to bf16, glu_act -> bf16
+//   down: y[s, col] = acc * sa[s] * ws[e*H + col], fp32
+// (k_gemm_fp8's order of the two scale products.)  No atomics.
+// ====================================================================
+
+typedef long i64x2 __attribute__((ext_vector_type(2)));
+
+template <int TM, bool GLU>
+DEVINL void moe_gemm_fp8_tile(uint8_t* As, uint8_t* Bs,
+                              const uint8_t* __restrict__ Xq,
+                              const float* __restrict__ sx,
+                              const int* __restrict__ slot_row,
+                              const uint8_t* __restrict__ Wall,
+                              const float* __restrict__ WSall,
+                              const int* __restrict__ tiles,
+                              u16* __restrict__ outb,
+                              float* __restrict__ outf, int N, int K,
+                              int act) {
+  constexpr int WR = TM >= 128 ? 2 : 1, WC = 4 / WR;  // wave grid
+  constexpr int SUBM = TM / WR;        // rows per wave
+  constexpr int FM = SUBM / 16;        // A fragments per wave
+  constexpr int FB = 128 / (16 * WC);  // B fragments per wave
+  constexpr int FN = FB / 2;           // GLU: gate (and up) fragments
+  constexpr int TN = GLU ? 64 : 128;   // output columns per block
+  constexpr int AI = TM / 32;          // A staging calls per wave
+  constexpr int KB = 128;              // bytes (= elements) per K step
+  const int ti = blockIdx.x;
+  if (ti >= tiles[0]) return;
+  const int e = tiles[1 + 3 * ti], first = tiles[2 + 3 * ti];
+  const int rows = tiles[3 + 3 * ti];
+  const int n0 = blockIdx.y * TN;
+  const uint8_t* W = Wall + (size_t)e * (GLU ? 2 : 1) * N * K;
+  const float* ws = WSall + (size_t)e * (GLU ? 2 : 1) * N;
+
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int wrow = wave / WC, wcol = wave % WC;
+  const int g_r = lane >> 3, g_s = lane & 7;
+  // every staged row r has r & 7 == g_r, so a lane's source chunk is the
+  // same for all of its A and B rows
+  const int sc = g_s ^ g_r;
+  const int hback = (sc & 4) * 16;  // half step: chunks 4..7 -> 0..3
+
+  const uint8_t* ap[AI];
+  const uint8_t* bp[4];
+#pragma unroll
+  for (int i = 0; i < AI; i++) {
+    int r = wave * (TM / 4) + i * 8 + g_r;
+    int s = first + (r < rows ? r : rows - 1);
+    int src = GLU ? slot_row[s] : s;
+    ap[i] = Xq + (size_t)src * K + sc * 16;
+  }
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    int r = wave * 32 + i * 8 + g_r;  // B tile row 0..127
+    int c = n0 + (GLU ? (r & 63) : r);
+    c = c < N ? c : N - 1;
+    int wr = GLU ? (r >> 6) * N + c : c;
+    bp[i] = W + (size_t)wr * K + sc * 16;
+  }
+  auto stage = [&](int buf, int koff) {  // koff: per-lane byte offset
+#pragma unroll
+    for (int i = 0; i < AI; i++)
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) uint32_t*)(ap[i] + koff),
+          (__attribute__((address_space(3))) uint32_t*)(
+              As + buf * (TM * KB) + (wave * (TM / 4) + i * 8) * KB),
+          16, 0, 0);
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) uint32_t*)(bp[i] + koff),
+          (__attribute__((address_space(3))) uint32_t*)(
+              Bs + buf * (128 * KB) + (wave * 32 + i * 8) * KB),
+          16, 0, 0);
+  };
+
+  f4v acc[FM][FB];
+#pragma unroll
+  for (int i = 0; i < FM; i++)
+#pragma unroll
+    for (int j = 0; j < FB; j++) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+
+  const int nt = (K + KB - 1) / KB;
+  const bool half = (K % KB) != 0;  // the last step is 64 bytes deep
+  stage(0, (half && nt == 1) ? -hback : 0);
+  __syncthreads();
+  const int fr = lane & 15, fk = lane >> 4;
+  int cur = 0;
+  for (int t = 0; t < nt; t++) {
+    const uint8_t* Ac = As + cur * (TM * KB);
+    const uint8_t* Bc = Bs + cur * (128 * KB);
+    // All of this step's fragments come out of LDS BEFORE the next
+    // step's DMA is issued: the compiler puts a vmcnt(0) in front of any
+    // LDS read that follows a global_load_lds, and this order moves that
+    // wait behind the MFMAs, so the loads fly while the step computes.
+    // (A half step reads its unused chunks too: defined LDS, no MFMA.)
+    i64x2 a[2][FM], b[2][FB];
+#pragma unroll
+    for (int hf = 0; hf < 2; hf++) {
+#pragma unroll
+      for (int i = 0; i < FM; i++) {
+        int ra = wrow * SUBM + i * 16 + fr;
+        a[hf][i] = *(const i64x2*)(Ac + ra * KB +
+                                   (((hf * 4 + fk) ^ (ra & 7)) * 16));
+      }
+#pragma unroll
+      for (int j = 0; j < FB; j++) {
+        int rb = GLU ? (j / FN) * 64 + wcol * (FN * 16) + (j % FN) * 16 + fr
+                     : wcol * (FB * 16) + j * 16 + fr;
+        b[hf][j] = *(const i64x2*)(Bc + rb * KB +
+                                   (((hf * 4 + fk) ^ (rb & 7)) * 16));
+      }
+    }
+    if (t + 1 < nt)
+      stage(cur ^ 1, (t + 1) * KB - ((half && t + 2 == nt) ? hback : 0));
+    const int nh = (half && t + 1 == nt) ? 1 : 2;  // block-uniform
+#pragma unroll
+    for (int hf = 0; hf < 2; hf++) {
+      if (hf < nh) {
+#pragma unroll
+        for (int q = 0; q < 2; q++)
+#pragma unroll
+          for (int i = 0; i < FM; i++)
+#pragma unroll
+            for (int j = 0; j < FB; j++)
+              acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(
+                  a[hf][i][q], b[hf][j][q], acc[i][j], 0, 0, 0);
+      }
+    }
+    __syncthreads();  // drains the DMA of the next tile; read fence
+    cur ^= 1;
+  }
+
+  // C layout: col = lane & 15, row = (lane >> 4) * 4 + reg
+  const int cc = lane & 15, cr = (lane >> 4) * 4;
+  float wsc[FB];
+#pragma unroll
+  for (int j = 0; j < FB; j++) {
+    int col = GLU ? n0 + wcol * (FN * 16) + (j % FN) * 16 + cc
+                  : n0 + wcol * (FB * 16) + j * 16 + cc;
+    wsc[j] = col < N ? ws[(GLU ? (j / FN) * N : 0) + col] : 0.f;
+  }
+#pragma unroll
+  for (int i = 0; i < FM; i++) {
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int row = wrow * SUBM + i * 16 + cr + r;
+      if (row >= rows) continue;
+      const int s = first + row;
+      const float sr = sx[GLU ? slot_row[s] : s];
+      const size_t o = (size_t)s * N;
+      if (GLU) {
+#pragma unroll
+        for (int j = 0; j < FN; j++) {
+          int col = n0 + wcol * (FN * 16) + j * 16 + cc;
+          if (col < N) {
+            const float g = acc[i][j][r] * sr * wsc[j];
+            const float u = acc[i][j + FN][r] * sr * wsc[j + FN];
+            outb[o + col] = glu_act(b2f(f2b(g)), b2f(f2b(u)), act);
+          }
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < FB; j++) {
+          int col = n0 + wcol * (FB * 16) + j * 16 + cc;
+          if (col < N) outf[o + col] = acc[i][j][r] * sr * wsc[j];
+        }
+      }
+    }
+  }
+}
+
+template <int TM>
+MOE_KERNEL(256)
+k_moe_gemm_fp8_glu_t(const uint8_t* __restrict__ xq,
+                     const float* __restrict__ sx,
+                     const int* __restrict__ slot_row,
+                     const uint8_t* __restrict__ wgu_q_all,
+                     const float* __restrict__ wgu_s_all,
+                     const int* __restrict__ tiles, u16* __restrict__ actb,
+                     int I, int H, int act) {
+  __shared__ uint8_t As[2 * TM * 128];
+  __shared__ uint8_t Bs[2 * 128 * 128];
+  moe_gemm_fp8_tile<TM, true>(As, Bs, xq, sx, slot_row, wgu_q_all, wgu_s_all,
+                              tiles, actb, nullptr, I, H, act);
+}
+
+template <int TM>
+MOE_KERNEL(256)
+k_moe_gemm_fp8_down_t(const uint8_t* __restrict__ actq,
+                      const float* __restrict__ sa,
+                      const uint8_t* __restrict__ wdown_q_all,
+                      const float* __restrict__ wdown_s_all,
+                      const int* __restrict__ tiles, float* __restrict__ y,
+                      int H, int I) {
+  __shared__ uint8_t As[2 * TM * 128];
+  __shared__ uint8_t Bs[2 * 128 * 128];
+  moe_gemm_fp8_tile<TM, false>(As, Bs, actq, sa, nullptr, wdown_q_all,
+                               wdown_s_all, tiles, nullptr, y, H, I, 0);
+}
+
+extern "C" hipError_t launch_moe_gemm_fp8_glu(
+    const void* xq, const void* sx, const void* slot_row,
+    const void* wgu_q_all, const void* wgu_s_all, const void* tiles,
+    void* actb, int M, int topk, int E, int H, int I, int act, int tm,
+    hipStream_t stream) {
+  if (!moe_gemm_args_ok(M, topk, E, H, I, tm) || H % 64 != 0)
+    return hipErrorInvalidValue;
+  dim3 grid((M * topk + tm - 1) / tm + E, (I + 63) / 64);
+#define MOE_GLU8_LAUNCH(TMV)                                                 \
+  hipLaunchKernelGGL((k_moe_gemm_fp8_glu_t<TMV>), grid, dim3(256), 0,        \
+                     stream, (const uint8_t*)xq, (const float*)sx,           \
+                     (const int*)slot_row, (const uint8_t*)wgu_q_all,        \
+                     (const float*)wgu_s_all, (const int*)tiles, (u16*)actb, \
+                     I, H, act)
+  if (tm == MOE_TMP) MOE_GLU8_LAUNCH(MOE_TMP); else MOE_GLU8_LAUNCH(MOE_TMS);
+#undef MOE_GLU8_LAUNCH
+  return hipGetLastError();
+}
+
+extern "C" hipError_t launch_moe_gemm_fp8_down(
+    const void* actq, const void* sa, const void* wdown_q_all,
+    const void* wdown_s_all, const void* tiles, void* y, int M, int topk,
+    int E, int H, int I, int tm, hipStream_t stream) {
+  if (!moe_gemm_args_ok(M, topk, E, H, I, tm) || I % 64 != 0)
+    return hipErrorInvalidValue;
+  dim3 grid((M * topk + tm - 1) / tm + E, (H + 127) / 128);
+#define MOE_DOWN8_LAUNCH(TMV)                                              \
+  hipLaunchKernelGGL((k_moe_gemm_fp8_down_t<TMV>), grid, dim3(256), 0,     \
+                     stream, (const uint8_t*)actq, (const float*)sa,       \
+                     (const uint8_t*)wdown_q_all,                          \
+                     (const float*)wdown_s_all, (const int*)tiles,         \
+                     (float*)y, H, I)
+  if (tm == MOE_TMP) MOE_DOWN8_LAUNCH(MOE_TMP); else MOE_DOWN8_LAUNCH(MOE_TMS);
+#undef MOE_DOWN8_LAUNCH
+  return hipGetLastError();
+}
+
 // h[m, :] = bf16(h[m, :] + sum_j slot_w[s_j] * y[s_j, :]), s_j the row's
 // slots in ascending order (= ascending expert), fp32 throughout.  One
 // block per row: nobody else writes that row, so plain stores.

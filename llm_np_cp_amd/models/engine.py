@@ -89,10 +89,11 @@ class GPUModel:
         bf16, ``max_batch>1``, single-GPU, non-MoE engine up to B = 16
         on the bf16 skinny MFMA GEMM (`_proj_skinny_bf16`); ignored for
         every other engine.  ``moe_grouped`` (None = env LLM_MOE_GROUPED,
-        default off) runs the prefill / lockstep-row MLP of a bf16,
-        single-GPU MoE engine on the token-grouped expert GEMMs
-        (`_moe_mlp_rows_grouped`) instead of the dense per-expert loop;
-        ignored for every other engine (fp8 experts keep the loop)."""
+        default off) runs the prefill / lockstep-row MLP of a bf16 or
+        fp8, single-GPU MoE engine on the token-grouped expert GEMMs
+        (`_moe_mlp_rows_grouped`; fp8 engines: e4m3 x e4m3 MFMA on the
+        single weight copy) instead of the dense per-expert loop;
+        ignored for every other engine."""
         if not torch.cuda.is_available():
             raise RuntimeError("GPUModel requires a GPU (MI355X)")
         self.config = config
@@ -131,7 +132,7 @@ class GPUModel:
             import os as _os
             moe_grouped = _os.environ.get("LLM_MOE_GROUPED", "0").strip() \
                 not in ("", "0")
-        self.moe_grouped = bool(moe_grouped and dtype == "bf16"
+        self.moe_grouped = bool(moe_grouped and dtype in ("bf16", "fp8")
                                 and config.is_moe)
         if kv_dtype not in ("bf16", "fp8"):
             raise ValueError(f"unsupported kv_dtype {kv_dtype!r}")
@@ -572,6 +573,14 @@ class GPUModel:
                 self.moe_act = torch.zeros(NP, I, **bf)
                 self.moe_y = torch.zeros(NP, H, dtype=torch.float32,
                                          device=dev)
+                if self.fp8:
+                    # e4m3 GLU output per slot; xn is quantised into
+                    # b_xq / b_sx, seen here as [PC, H] rows
+                    self.moe_actq = torch.zeros(NP, I, dtype=torch.uint8,
+                                                device=dev)
+                    self.moe_sa = torch.zeros(NP, dtype=torch.float32,
+                                              device=dev)
+                    self.moe_xq = self.b_xq[:PC * H].view(PC, H)
         self.b_hb = torch.zeros(H, **bf)   # gemma residual ping-pong
         self.b_t2 = torch.zeros(H, **bf)   # gemma ffn-out delta
         self.b_gu = torch.zeros(2 * I, **bf)
@@ -892,7 +901,10 @@ class GPUModel:
         launch over all experts (A gathered through the sort, GLU in the
         epilogue) -> ONE down GEMM launch (fp32 per slot) -> combine into
         h in ascending expert order.  5 launches per layer, no host
-        read; the tile height follows M * topk / E (`ho.moe_tile_rows`)."""
+        read; the tile height follows M * topk / E (`ho.moe_tile_rows`).
+        fp8 engines run both GEMMs on e4m3 operands: xn is quantised
+        once per layer (not per expert) and the GLU output once over its
+        M * topk slots, 7 launches whatever E is."""
         E, k = self.config.num_local_experts, self.topk
         ho.moe_route(self.b_h, lw["g_post"], lw["wg"], M, k, self.moe_idx,
                      self.moe_w, eps=self.config.rms_norm_eps)
@@ -900,6 +912,20 @@ class GPUModel:
                           self.moe_slot_row, self.moe_slot_w,
                           self.moe_pair_slot, self.moe_grp_off,
                           self.moe_tiles)
+        if self.fp8:
+            n = M * k
+            ho.quant_fp8(self.b_xn[:M], self.b_xq, self.b_sx)
+            ho.moe_gemm_fp8_glu(self.moe_xq, self.b_sx, self.moe_slot_row,
+                                lw["wgu_q_all"], lw["wgu_s_all"],
+                                self.moe_tiles, self.moe_act, M, k, tm,
+                                act=self.act)
+            ho.quant_fp8(self.moe_act[:n], self.moe_actq, self.moe_sa)
+            ho.moe_gemm_fp8_down(self.moe_actq, self.moe_sa,
+                                 lw["wdown_q_all"], lw["wdown_s_all"],
+                                 self.moe_tiles, self.moe_y, M, k, tm)
+            ho.moe_combine(self.b_h, self.moe_y, self.moe_pair_slot,
+                           self.moe_slot_w, M, k)
+            return
         ho.moe_gemm_glu(self.b_xn, self.moe_slot_row, lw["wgu_all"],
                         self.moe_tiles, self.moe_act, M, k, tm,
                         act=self.act)

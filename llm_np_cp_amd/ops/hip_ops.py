@@ -171,6 +171,10 @@ _SIGS = {
                             [ctypes.c_void_p],
     "launch_moe_combine": [ctypes.c_void_p] * 4 + [ctypes.c_int] * 3 +
                           [ctypes.c_void_p],
+    "launch_moe_gemm_fp8_glu": [ctypes.c_void_p] * 7 + [ctypes.c_int] * 7 +
+                               [ctypes.c_void_p],
+    "launch_moe_gemm_fp8_down": [ctypes.c_void_p] * 6 + [ctypes.c_int] * 6 +
+                                [ctypes.c_void_p],
     # one-shot xGMI collectives (csrc/xgmi_comm.hip)
     "launch_xgmi_coll": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                          ctypes.c_int, ctypes.c_int, ctypes.c_long,
@@ -1520,6 +1524,85 @@ def moe_gemm_down(act_in: torch.Tensor, wdown_all: torch.Tensor,
     _check(lib().launch_moe_gemm_down(
         _ptr(act_in), _ptr(wdown_all), _ptr(tiles), _ptr(y), M, topk, E, H,
         I, tm, _stream()), "moe_gemm_down")
+
+
+def _moe_fp8_operands(name, a, sa, rows, w, ws):
+    """Common checks of an e4m3 A [>= rows, K] / B [N, K] pair with
+    per-row fp32 scales; returns K."""
+    for what, t in (("activations", a), ("weights", w)):
+        if (t.dim() != 2 or t.dtype != torch.uint8 or not t.is_cuda
+                or not t.is_contiguous()):
+            raise ValueError(f"{name}: {what} must be contiguous 2-D uint8 "
+                             f"(e4m3 bytes) on the GPU")
+    K = a.shape[1]
+    if K % 64 != 0 or w.shape[1] != K:
+        raise ValueError(f"{name}: K={K} must be a multiple of 64 and match "
+                         f"the weights {tuple(w.shape)}")
+    if a.shape[0] < rows:
+        raise ValueError(f"{name}: activations have {a.shape[0]} rows < "
+                         f"{rows}")
+    _moe_buf(name, "activation scales", sa, torch.float32, rows)
+    if ws.numel() != w.shape[0]:
+        raise ValueError(f"{name}: {ws.numel()} weight scales for "
+                         f"{w.shape[0]} weight rows")
+    _moe_buf(name, "weight scales", ws, torch.float32, w.shape[0])
+    return K
+
+
+def moe_gemm_fp8_glu(xq: torch.Tensor, sx: torch.Tensor,
+                     slot_row: torch.Tensor, wgu_q_all: torch.Tensor,
+                     wgu_s_all: torch.Tensor, tiles: torch.Tensor,
+                     act_out: torch.Tensor, M: int, topk: int, tm: int,
+                     act: int = 0):
+    """``moe_gemm_glu`` on e4m3 operands (fp8 x fp8 MFMA): g/u =
+    (xq[slot_row[s]] @ Wq^T) * sx[slot_row[s]] * ws[row], each rounded
+    to bf16, act_out[s] = act(g) * u in bf16.  xq [>= M, H] uint8 with
+    sx [>= M] fp32 (one ``quant_fp8`` of the normed rows); wgu_q_all
+    [E*2I, H] uint8, per expert [gate; up], wgu_s_all [E*2I] fp32."""
+    name = "moe_gemm_fp8_glu"
+    H = _moe_fp8_operands(name, xq, sx, M, wgu_q_all, wgu_s_all)
+    if act_out.dim() != 2:
+        raise ValueError(f"{name}: act_out must be [slots, I]")
+    I = act_out.shape[1]
+    if I < 64 or wgu_q_all.shape[0] % (2 * I) != 0:
+        raise ValueError(f"{name}: wgu_q_all rows {wgu_q_all.shape[0]} are "
+                         f"not E blocks of 2*I, I={I} >= 64")
+    E = wgu_q_all.shape[0] // (2 * I)
+    _moe_dims(name, M, topk, E, tm)
+    _moe_buf(name, "slot_row", slot_row, torch.int32, M * topk)
+    _moe_buf(name, "tiles", tiles, torch.int32,
+             1 + 3 * moe_max_tiles(M, topk, E, tm))
+    _moe_buf(name, "act_out", act_out, torch.bfloat16, M * topk * I)
+    _check(lib().launch_moe_gemm_fp8_glu(
+        _ptr(xq), _ptr(sx), _ptr(slot_row), _ptr(wgu_q_all), _ptr(wgu_s_all),
+        _ptr(tiles), _ptr(act_out), M, topk, E, H, I, act, tm, _stream()),
+        name)
+
+
+def moe_gemm_fp8_down(actq: torch.Tensor, sa: torch.Tensor,
+                      wdown_q_all: torch.Tensor, wdown_s_all: torch.Tensor,
+                      tiles: torch.Tensor, y: torch.Tensor, M: int,
+                      topk: int, tm: int):
+    """``moe_gemm_down`` on e4m3 operands: y[s, :H] (fp32) =
+    (actq[s] @ Wdq[e(s)]^T) * sa[s] * ws[row].  actq [>= M*topk, I]
+    uint8 in slot order with sa [>= M*topk] fp32 (``quant_fp8`` of the
+    GLU output); wdown_q_all [E*H, I] uint8, wdown_s_all [E*H] fp32."""
+    name = "moe_gemm_fp8_down"
+    if y.dim() != 2:
+        raise ValueError(f"{name}: y must be [slots, H]")
+    I = _moe_fp8_operands(name, actq, sa, M * topk, wdown_q_all, wdown_s_all)
+    H = y.shape[1]
+    if H < 64 or H % 4 != 0 or wdown_q_all.shape[0] % H != 0:
+        raise ValueError(f"{name}: wdown_q_all rows {wdown_q_all.shape[0]} "
+                         f"are not E blocks of H={H}")
+    E = wdown_q_all.shape[0] // H
+    _moe_dims(name, M, topk, E, tm)
+    _moe_buf(name, "tiles", tiles, torch.int32,
+             1 + 3 * moe_max_tiles(M, topk, E, tm))
+    _moe_buf(name, "y", y, torch.float32, M * topk * H)
+    _check(lib().launch_moe_gemm_fp8_down(
+        _ptr(actq), _ptr(sa), _ptr(wdown_q_all), _ptr(wdown_s_all),
+        _ptr(tiles), _ptr(y), M, topk, E, H, I, tm, _stream()), name)
 
 
 def moe_combine(h: torch.Tensor, y: torch.Tensor, pair_slot: torch.Tensor,
