@@ -1799,13 +1799,21 @@ k_gemv_fp4_t(const uint8_t* __restrict__ W, const uint8_t* __restrict__ E,
              const float* __restrict__ g, const float* __restrict__ g2,
              void* __restrict__ y, const u16* __restrict__ res, int N, int K,
              int stage, int act, float eps, int out_f32, float softcap,
-             float escale) {
+             float escale, const int* __restrict__ eidx, long wstride,
+             const float* __restrict__ oscale) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const float* xv = XDIR ? nullptr
                          : gemv_stage_f32(smem, x, x2, g, g2, (u16*)res, K,
                                           stage, act, eps, escale);
   const u16* eres = (stage == STAGE_NORM2 || stage == STAGE_NORM_EMBED)
                         ? nullptr : res;
+  // MoE: expert-indexed base (wstride in ELEMENTS: 2 per packed byte,
+  // 32 per scale byte) + device output scale, as k_gemv_fp8_t
+  if (eidx) {
+    W += (size_t)(*eidx) * (wstride >> 1);
+    E += (size_t)(*eidx) * (wstride >> 5);
+  }
+  const float osc = oscale ? *oscale : 1.0f;
 
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int wpb = blockDim.x >> 6;
@@ -1908,7 +1916,7 @@ k_gemv_fp4_t(const uint8_t* __restrict__ W, const uint8_t* __restrict__ E,
 #pragma unroll
   for (int r = 0; r < RPW; r++) {
     f2v s = a0[r] + a1[r];
-    float acc = wave_reduce_sum(s[0] + s[1]);
+    float acc = osc * wave_reduce_sum(s[0] + s[1]);
     if (lane == 0 && row0 + r < N)
       gemv_epilogue(acc, row0 + r, y, eres, out_f32, softcap);
   }
@@ -1922,8 +1930,11 @@ extern "C" hipError_t launch_gemv_fp4(const void* W, const void* E,
                                       int stage, int act, float eps,
                                       int out_f32, float softcap, int nt,
                                       int rpw, int maxblocks, float escale,
+                                      const void* eidx, long wstride,
+                                      const void* oscale,
                                       hipStream_t stream) {
-  if (K % 32 != 0) return hipErrorInvalidValue;
+  if (K % 32 != 0 || (eidx && wstride % 32 != 0))
+    return hipErrorInvalidValue;
   static int xdir_raw4 = -1, rpw_env4 = -1;
   if (xdir_raw4 < 0) {
     const char* e = getenv("LLM_GEMV_XDIR");
@@ -1959,7 +1970,8 @@ extern "C" hipError_t launch_gemv_fp4(const void* W, const void* E,
                      dim3(threads), lds, stream, (const uint8_t*)W,         \
                      (const uint8_t*)E, (const u16*)x, (const u16*)x2,      \
                      (const float*)g, (const float*)g2, y, (const u16*)res, \
-                     N, K, stage, act, eps, out_f32, softcap, escale)
+                     N, K, stage, act, eps, out_f32, softcap, escale,       \
+                     (const int*)eidx, wstride, (const float*)oscale)
   if (xdir) {
     if (nt && rpw == 2) GEMV4_CASE(true, 2, true);
     else if (nt) GEMV4_CASE(true, 1, true);
@@ -6395,6 +6407,293 @@ extern "C" hipError_t launch_moe_gemm_fp8_down(
                      (float*)y, H, I)
   if (tm == MOE_TMP) MOE_DOWN8_LAUNCH(MOE_TMP); else MOE_DOWN8_LAUNCH(MOE_TMS);
 #undef MOE_DOWN8_LAUNCH
+  return hipGetLastError();
+}
+
+// ====================================================================
+// The grouped GEMMs on the engine's MXFP4 experts: A = e4m3 rows (one
+// quant_fp8, per-row scale in the epilogue), B = the e2m1 nibbles and
+// e8m0 block scales exactly as k_quant_fp4_rows writes them, multiplied
+// by v_mfma_scale_f32_16x16x128_f8f6f4 (k_gemm_fp4_skinny's operand
+// layout).  Sort, tile table, grid, wave grids and epilogue rounding
+// points are the fp8 pair's; the tile body differs:
+//   - one K step is 128 elements = ONE scaled MFMA per fragment pair.
+//     A: TM x 128 B per buffer, staged and swizzled as the fp8 body;
+//     lane (fr = lane & 15, g = lane >> 4) reads chunks g and 4 + g of
+//     row fr -> operand VGPRs 0-3 = [k+16g, +16), 4-7 = [k+64+16g, +16).
+//   - B: 128 rows x 64 B per buffer.  One wave DMA call lands 16 whole
+//     rows (lane l -> row l >> 2, chunk l & 3), two calls per wave per
+//     step; no swizzle: lane (fr, g) reads LDS offset fr*64 + g*16, the
+//     wave's 64 reads are contiguous.  That chunk is elements
+//     [k+32g, +32) = one MX block, so the lane's scale byte
+//     E[row][(k >> 5) + g] is its own: a byte load from global straight
+//     into a register, issued one step ahead.  LDS: 48 KB / 24 KB.
+//   - every (A, B) fragment pair runs the MFMA twice, on the
+//     fp4sk_x_hi / fp4sk_x_lo halves of A with an accumulator each
+//     (summed in the epilogue): see fp4sk_x_hi.
+//   - K % 64 == 0: in a last 64-element step the DMA source of A chunks
+//     4..7 and of B chunks 2..3 steps back inside the row (nothing is
+//     read past a row), the A high half is zeroed, and lanes g >= 2 pass
+//     zero B data with scale 127 and load no scale byte.  Block-uniform.
+//   glu:  g = acc_g * sx[slot_row[s]], u likewise, each rounded to bf16,
+//         glu_act -> bf16;  down: y[s, col] = acc * sa[s], fp32
+// No atomics, no split-K.  MOE_FP4_ONE_MFMA (timing builds only, wrong
+// results for small activations) compiles the second MFMA out.
+// ====================================================================
+
+template <int TM, bool GLU>
+DEVINL void moe_gemm_fp4_tile(uint8_t* As, uint8_t* Bs,
+                              const uint8_t* __restrict__ Xq,
+                              const float* __restrict__ sx,
+                              const int* __restrict__ slot_row,
+                              const uint8_t* __restrict__ W4all,
+                              const uint8_t* __restrict__ E4all,
+                              const int* __restrict__ tiles,
+                              u16* __restrict__ outb,
+                              float* __restrict__ outf, int N, int K,
+                              int act) {
+  constexpr int WR = TM >= 128 ? 2 : 1, WC = 4 / WR;  // wave grid
+  constexpr int SUBM = TM / WR;        // rows per wave
+  constexpr int FM = SUBM / 16;        // A fragments per wave
+  constexpr int FB = 128 / (16 * WC);  // B fragments per wave
+  constexpr int FN = FB / 2;           // GLU: gate (and up) fragments
+  constexpr int TN = GLU ? 64 : 128;   // output columns per block
+  constexpr int AI = TM / 32;          // A staging calls per wave
+  constexpr int KA = 128, KW = 64;     // bytes per K step: A row, B row
+  const int ti = blockIdx.x;
+  if (ti >= tiles[0]) return;
+  const int e = tiles[1 + 3 * ti], first = tiles[2 + 3 * ti];
+  const int rows = tiles[3 + 3 * ti];
+  const int n0 = blockIdx.y * TN;
+  const size_t wrow0 = (size_t)e * (GLU ? 2 : 1) * N;  // expert's first row
+  const uint8_t* W = W4all + wrow0 * (K >> 1);
+  const uint8_t* Es = E4all + wrow0 * (K >> 5);
+
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int wrow = wave / WC, wcol = wave % WC;
+  const int g_r = lane >> 3, g_s = lane & 7;  // A staging: row, LDS chunk
+  const int sc = g_s ^ g_r;                   // its source chunk
+  const int hback = (sc & 4) * 16;   // half step: A chunks 4..7 -> 0..3
+  const int b_r = lane >> 2, b_c = lane & 3;  // B staging: row, chunk
+  const int bback = (b_c & 2) * 16;  // half step: B chunks 2..3 -> 0..1
+
+  // tile row r (0..127) of the B tile -> weight row of this expert
+  auto wrow_of = [&](int r) {
+    int c = n0 + (GLU ? (r & 63) : r);
+    c = c < N ? c : N - 1;
+    return GLU ? (r >> 6) * N + c : c;
+  };
+  const uint8_t* ap[AI];
+  const uint8_t* bp[2];
+#pragma unroll
+  for (int i = 0; i < AI; i++) {
+    int r = wave * (TM / 4) + i * 8 + g_r;
+    int s = first + (r < rows ? r : rows - 1);
+    int src = GLU ? slot_row[s] : s;
+    ap[i] = Xq + (size_t)src * K + sc * 16;
+  }
+#pragma unroll
+  for (int i = 0; i < 2; i++)
+    bp[i] = W + (size_t)wrow_of(wave * 32 + i * 16 + b_r) * (K >> 1) +
+            b_c * 16;
+  auto stage = [&](int buf, int t, bool hs) {  // step t; hs: a half step
+    const int ka = t * KA - (hs ? hback : 0);
+    const int kw = t * KW - (hs ? bback : 0);
+#pragma unroll
+    for (int i = 0; i < AI; i++)
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) uint32_t*)(ap[i] + ka),
+          (__attribute__((address_space(3))) uint32_t*)(
+              As + buf * (TM * KA) + (wave * (TM / 4) + i * 8) * KA),
+          16, 0, 0);
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) uint32_t*)(bp[i] + kw),
+          (__attribute__((address_space(3))) uint32_t*)(
+              Bs + buf * (128 * KW) + (wave * 32 + i * 16) * KW),
+          16, 0, 0);
+  };
+
+  const int fr = lane & 15, g = lane >> 4;
+  int rbt[FB];               // the lane's B tile row per fragment
+  const uint8_t* ep[FB];     // and that row's scale bytes, at k-group g
+#pragma unroll
+  for (int j = 0; j < FB; j++) {
+    rbt[j] = GLU ? (j / FN) * 64 + wcol * (FN * 16) + (j % FN) * 16 + fr
+                 : wcol * (FB * 16) + j * 16 + fr;
+    ep[j] = Es + (size_t)wrow_of(rbt[j]) * (K >> 5) + g;
+  }
+
+  f4v acc[FM][FB], acl[FM][FB];  // large / small X elements
+#pragma unroll
+  for (int i = 0; i < FM; i++)
+#pragma unroll
+    for (int j = 0; j < FB; j++) {
+      acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+      acl[i][j] = {0.f, 0.f, 0.f, 0.f};
+    }
+
+  const int nt = (K + KA - 1) / KA;
+  const bool half = (K % KA) != 0;  // the last step is 64 elements deep
+  // a lane whose MX block lies at or beyond K loads no scale byte: 127
+  // (= 1.0; a stray 0xFF would be NaN) for the zero data it passes
+  int sb[FB];
+#pragma unroll
+  for (int j = 0; j < FB; j++) sb[j] = g * 32 < K ? (int)ep[j][0] : 127;
+  stage(0, 0, half && nt == 1);
+  __syncthreads();
+  int cur = 0;
+  for (int t = 0; t < nt; t++) {
+    const uint8_t* Ac = As + cur * (TM * KA);
+    const uint8_t* Bc = Bs + cur * (128 * KW);
+    // fragments out of LDS first, then the next step's scale bytes and
+    // DMA, then the MFMAs (the fp8 body's order: the vmcnt wait a later
+    // LDS read would need lands behind the math)
+    u4v_ alo[FM], ahi[FM], b[FB];
+#pragma unroll
+    for (int i = 0; i < FM; i++) {
+      const int ra = wrow * SUBM + i * 16 + fr;
+      alo[i] = *(const u4v_*)(Ac + ra * KA + ((g ^ (ra & 7)) * 16));
+      ahi[i] = *(const u4v_*)(Ac + ra * KA + (((4 + g) ^ (ra & 7)) * 16));
+    }
+#pragma unroll
+    for (int j = 0; j < FB; j++)
+      b[j] = *(const u4v_*)(Bc + rbt[j] * KW + g * 16);
+    int sbn[FB];
+#pragma unroll
+    for (int j = 0; j < FB; j++) sbn[j] = 127;
+    if (t + 1 < nt) {
+#pragma unroll
+      for (int j = 0; j < FB; j++)
+        if ((t + 1) * KA + g * 32 < K) sbn[j] = ep[j][(t + 1) * 4];
+      stage(cur ^ 1, t + 1, half && t + 2 == nt);
+    }
+    const bool hs = half && t + 1 == nt;  // block-uniform
+    const u4v_ z = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < FM; i++) {
+      const i8v a = fp4sk_pack_x(alo[i], hs ? z : ahi[i]);
+      const i8v a_hi = fp4sk_x_hi(a);
+#ifndef MOE_FP4_ONE_MFMA
+      const i8v a_lo = fp4sk_x_lo(a);
+#endif
+#pragma unroll
+      for (int j = 0; j < FB; j++) {
+        const u4v_ w = (hs && g >= 2) ? z : b[j];
+        const i8v bw = {(int)w[0], (int)w[1], (int)w[2], (int)w[3],
+                        0, 0, 0, 0};
+#ifndef MOE_FP4_ONE_MFMA
+        acc[i][j] = FP4SK_MFMA(a_hi, bw, acc[i][j], sb[j]);
+        acl[i][j] = FP4SK_MFMA(a_lo, bw, acl[i][j], sb[j]);
+#else
+        acc[i][j] = FP4SK_MFMA(a, bw, acc[i][j], sb[j]);
+        (void)a_hi;
+#endif
+      }
+    }
+    __syncthreads();  // drains the DMA of the next tile; read fence
+    cur ^= 1;
+#pragma unroll
+    for (int j = 0; j < FB; j++) sb[j] = sbn[j];
+  }
+
+  // C layout: col = lane & 15, row = (lane >> 4) * 4 + reg
+  const int cc = lane & 15, cr = (lane >> 4) * 4;
+#pragma unroll
+  for (int i = 0; i < FM; i++) {
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int row = wrow * SUBM + i * 16 + cr + r;
+      if (row >= rows) continue;
+      const int s = first + row;
+      const float sr = sx[GLU ? slot_row[s] : s];
+      const size_t o = (size_t)s * N;
+      if (GLU) {
+#pragma unroll
+        for (int j = 0; j < FN; j++) {
+          int col = n0 + wcol * (FN * 16) + j * 16 + cc;
+          if (col < N) {
+            const float gv = (acc[i][j][r] + acl[i][j][r]) * sr;
+            const float uv = (acc[i][j + FN][r] + acl[i][j + FN][r]) * sr;
+            outb[o + col] = glu_act(b2f(f2b(gv)), b2f(f2b(uv)), act);
+          }
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < FB; j++) {
+          int col = n0 + wcol * (FB * 16) + j * 16 + cc;
+          if (col < N) outf[o + col] = (acc[i][j][r] + acl[i][j][r]) * sr;
+        }
+      }
+    }
+  }
+}
+
+template <int TM>
+MOE_KERNEL(256)
+k_moe_gemm_fp4_glu_t(const uint8_t* __restrict__ xq,
+                     const float* __restrict__ sx,
+                     const int* __restrict__ slot_row,
+                     const uint8_t* __restrict__ wgu_q4_all,
+                     const uint8_t* __restrict__ wgu_e4_all,
+                     const int* __restrict__ tiles, u16* __restrict__ actb,
+                     int I, int H, int act) {
+  __shared__ __attribute__((aligned(16))) uint8_t As[2 * TM * 128];
+  __shared__ __attribute__((aligned(16))) uint8_t Bs[2 * 128 * 64];
+  moe_gemm_fp4_tile<TM, true>(As, Bs, xq, sx, slot_row, wgu_q4_all,
+                              wgu_e4_all, tiles, actb, nullptr, I, H, act);
+}
+
+template <int TM>
+MOE_KERNEL(256)
+k_moe_gemm_fp4_down_t(const uint8_t* __restrict__ actq,
+                      const float* __restrict__ sa,
+                      const uint8_t* __restrict__ wdown_q4_all,
+                      const uint8_t* __restrict__ wdown_e4_all,
+                      const int* __restrict__ tiles, float* __restrict__ y,
+                      int H, int I) {
+  __shared__ __attribute__((aligned(16))) uint8_t As[2 * TM * 128];
+  __shared__ __attribute__((aligned(16))) uint8_t Bs[2 * 128 * 64];
+  moe_gemm_fp4_tile<TM, false>(As, Bs, actq, sa, nullptr, wdown_q4_all,
+                               wdown_e4_all, tiles, nullptr, y, H, I, 0);
+}
+
+extern "C" hipError_t launch_moe_gemm_fp4_glu(
+    const void* xq, const void* sx, const void* slot_row,
+    const void* wgu_q4_all, const void* wgu_e4_all, const void* tiles,
+    void* actb, int M, int topk, int E, int H, int I, int act, int tm,
+    hipStream_t stream) {
+  if (!moe_gemm_args_ok(M, topk, E, H, I, tm) || H % 64 != 0)
+    return hipErrorInvalidValue;
+  dim3 grid((M * topk + tm - 1) / tm + E, (I + 63) / 64);
+#define MOE_GLU4_LAUNCH(TMV)                                               \
+  hipLaunchKernelGGL((k_moe_gemm_fp4_glu_t<TMV>), grid, dim3(256), 0,      \
+                     stream, (const uint8_t*)xq, (const float*)sx,         \
+                     (const int*)slot_row, (const uint8_t*)wgu_q4_all,     \
+                     (const uint8_t*)wgu_e4_all, (const int*)tiles,        \
+                     (u16*)actb, I, H, act)
+  if (tm == MOE_TMP) MOE_GLU4_LAUNCH(MOE_TMP); else MOE_GLU4_LAUNCH(MOE_TMS);
+#undef MOE_GLU4_LAUNCH
+  return hipGetLastError();
+}
+
+extern "C" hipError_t launch_moe_gemm_fp4_down(
+    const void* actq, const void* sa, const void* wdown_q4_all,
+    const void* wdown_e4_all, const void* tiles, void* y, int M, int topk,
+    int E, int H, int I, int tm, hipStream_t stream) {
+  if (!moe_gemm_args_ok(M, topk, E, H, I, tm) || I % 64 != 0)
+    return hipErrorInvalidValue;
+  dim3 grid((M * topk + tm - 1) / tm + E, (H + 127) / 128);
+#define MOE_DOWN4_LAUNCH(TMV)                                              \
+  hipLaunchKernelGGL((k_moe_gemm_fp4_down_t<TMV>), grid, dim3(256), 0,     \
+                     stream, (const uint8_t*)actq, (const float*)sa,       \
+                     (const uint8_t*)wdown_q4_all,                         \
+                     (const uint8_t*)wdown_e4_all, (const int*)tiles,      \
+                     (float*)y, H, I)
+  if (tm == MOE_TMP) MOE_DOWN4_LAUNCH(MOE_TMP); else MOE_DOWN4_LAUNCH(MOE_TMS);
+#undef MOE_DOWN4_LAUNCH
   return hipGetLastError();
 }
 

@@ -93,7 +93,10 @@ class GPUModel:
         fp8, single-GPU MoE engine on the token-grouped expert GEMMs
         (`_moe_mlp_rows_grouped`; fp8 engines: e4m3 x e4m3 MFMA on the
         single weight copy) instead of the dense per-expert loop;
-        ignored for every other engine."""
+        ignored for every other engine.  A ``dtype="fp4"`` MoE engine
+        has no dense loop: it is single-copy MXFP4 whatever ``max_batch``
+        is, and its rows always take the grouped path (scaled e4m3 x
+        e2m1 MFMA on the expert weights themselves)."""
         if not torch.cuda.is_available():
             raise RuntimeError("GPUModel requires a GPU (MI355X)")
         self.config = config
@@ -120,8 +123,8 @@ class GPUModel:
                 not in ("", "0")
         self.batch_fp4 = bool(batch_fp4 and self.wq4 and max_batch > 1
                               and not config.is_moe)
-        if self.batch_fp4:
-            self.keep_fp8 = False
+        if self.batch_fp4 or (self.wq4 and config.is_moe):
+            self.keep_fp8 = False  # fp4 MoE: never an fp8 copy
         if batch_skinny is None:
             import os as _os
             batch_skinny = _os.environ.get("LLM_BATCH_SKINNY", "0").strip() \
@@ -132,7 +135,9 @@ class GPUModel:
             import os as _os
             moe_grouped = _os.environ.get("LLM_MOE_GROUPED", "0").strip() \
                 not in ("", "0")
-        self.moe_grouped = bool(moe_grouped and dtype in ("bf16", "fp8")
+        # fp4 experts exist only in the grouped kernels: flag and env
+        # do not apply
+        self.moe_grouped = bool((moe_grouped or dtype == "fp4")
                                 and config.is_moe)
         if kv_dtype not in ("bf16", "fp8"):
             raise ValueError(f"unsupported kv_dtype {kv_dtype!r}")
@@ -144,8 +149,6 @@ class GPUModel:
         self.moe = config.is_moe
         self.topk = config.num_experts_per_tok
         if self.moe:
-            if self.wq4:
-                raise ValueError("MoE + fp4 weights not supported yet")
             if config.model_type == "gemma2":
                 raise ValueError("MoE is a llama-family (Mixtral) feature")
         self.rank, self.world = tpu.init_distributed()
@@ -458,7 +461,13 @@ class GPUModel:
                 # pointer by eidx * wstride device-side
                 lw["wg"] = bf16(w[f"{p}.block_sparse_moe.gate.weight"])
                 I2, H2 = 2 * self.inter_l, self.H
-                if self.fp8:
+                if self.wq4:
+                    # quantised once; decode views = the first expert
+                    for n, rows in (("wgu", I2), ("wdown", H2)):
+                        for sfx in ("_q4", "_e4"):
+                            lw[n + sfx + "_all"] = lw.pop(n + sfx)
+                            lw[n + sfx] = lw[n + sfx + "_all"][:rows]
+                elif self.fp8:
                     lw["wgu_q_all"] = lw.pop("wgu_q")
                     lw["wgu_s_all"] = lw.pop("wgu_s")
                     lw["wdown_q_all"] = lw.pop("wdown_q")
@@ -904,7 +913,9 @@ class GPUModel:
         read; the tile height follows M * topk / E (`ho.moe_tile_rows`).
         fp8 engines run both GEMMs on e4m3 operands: xn is quantised
         once per layer (not per expert) and the GLU output once over its
-        M * topk slots, 7 launches whatever E is."""
+        M * topk slots, 7 launches whatever E is.  fp4 engines run the
+        same 7 launches with the MXFP4 expert weights as the B operand
+        of the scaled MFMA (`ho.moe_gemm_fp4_glu` / `_down`)."""
         E, k = self.config.num_local_experts, self.topk
         ho.moe_route(self.b_h, lw["g_post"], lw["wg"], M, k, self.moe_idx,
                      self.moe_w, eps=self.config.rms_norm_eps)
@@ -914,15 +925,18 @@ class GPUModel:
                           self.moe_tiles)
         if self.fp8:
             n = M * k
+            glu, down, a, b = (
+                (ho.moe_gemm_fp4_glu, ho.moe_gemm_fp4_down, "_q4_all",
+                 "_e4_all") if self.wq4 else
+                (ho.moe_gemm_fp8_glu, ho.moe_gemm_fp8_down, "_q_all",
+                 "_s_all"))
             ho.quant_fp8(self.b_xn[:M], self.b_xq, self.b_sx)
-            ho.moe_gemm_fp8_glu(self.moe_xq, self.b_sx, self.moe_slot_row,
-                                lw["wgu_q_all"], lw["wgu_s_all"],
-                                self.moe_tiles, self.moe_act, M, k, tm,
-                                act=self.act)
+            glu(self.moe_xq, self.b_sx, self.moe_slot_row, lw["wgu" + a],
+                lw["wgu" + b], self.moe_tiles, self.moe_act, M, k, tm,
+                act=self.act)
             ho.quant_fp8(self.moe_act[:n], self.moe_actq, self.moe_sa)
-            ho.moe_gemm_fp8_down(self.moe_actq, self.moe_sa,
-                                 lw["wdown_q_all"], lw["wdown_s_all"],
-                                 self.moe_tiles, self.moe_y, M, k, tm)
+            down(self.moe_actq, self.moe_sa, lw["wdown" + a],
+                 lw["wdown" + b], self.moe_tiles, self.moe_y, M, k, tm)
             ho.moe_combine(self.b_h, self.moe_y, self.moe_pair_slot,
                            self.moe_slot_w, M, k)
             return
@@ -1889,7 +1903,17 @@ class GPUModel:
                     for j in range(self.topk):
                         ei = self.moe_idx[j:j + 1]
                         osc = self.moe_w[j:j + 1]
-                        if self.fp8:
+                        if self.wq4:
+                            ho.gemv_fp4(lw["wgu_q4"], lw["wgu_e4"], xn0,
+                                        self.b_gu, eidx=ei,
+                                        wstride=2 * I * H)
+                            ho.gemv_fp4(lw["wdown_q4"], lw["wdown_e4"],
+                                        self.b_gu[:I], h, res=h,
+                                        stage=ho.STAGE_GLU,
+                                        x2=self.b_gu[I:], act=self.act,
+                                        eidx=ei, wstride=H * I,
+                                        oscale=osc)
+                        elif self.fp8:
                             ho.gemv_fp8(lw["wgu_q"], lw["wgu_s"], xn0,
                                         self.b_gu, eidx=ei,
                                         wstride=2 * I * H, sstride=2 * I)

@@ -112,7 +112,8 @@ _SIGS = {
     "launch_gemv_fp4": [ctypes.c_void_p] * 8 + [ctypes.c_int] * 4 +
                        [ctypes.c_float, ctypes.c_int, ctypes.c_float,
                         ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                        ctypes.c_float, ctypes.c_void_p],
+                        ctypes.c_float, ctypes.c_void_p, ctypes.c_long,
+                        ctypes.c_void_p, ctypes.c_void_p],
     "launch_stage_quant_mx": [ctypes.c_void_p, ctypes.c_long,
                               ctypes.c_void_p, ctypes.c_long] +
                              [ctypes.c_void_p] * 4 +
@@ -174,6 +175,10 @@ _SIGS = {
     "launch_moe_gemm_fp8_glu": [ctypes.c_void_p] * 7 + [ctypes.c_int] * 7 +
                                [ctypes.c_void_p],
     "launch_moe_gemm_fp8_down": [ctypes.c_void_p] * 6 + [ctypes.c_int] * 6 +
+                                [ctypes.c_void_p],
+    "launch_moe_gemm_fp4_glu": [ctypes.c_void_p] * 7 + [ctypes.c_int] * 7 +
+                               [ctypes.c_void_p],
+    "launch_moe_gemm_fp4_down": [ctypes.c_void_p] * 6 + [ctypes.c_int] * 6 +
                                 [ctypes.c_void_p],
     # one-shot xGMI collectives (csrc/xgmi_comm.hip)
     "launch_xgmi_coll": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -1060,17 +1065,26 @@ def gemv_fp4(Wq: torch.Tensor, We: torch.Tensor, x: torch.Tensor,
              x2: torch.Tensor | None = None, g: torch.Tensor | None = None,
              act: int = 0, eps: float = 1e-5, nt: int = 1, rpw: int = 1,
              maxblocks: int = 0, g2: torch.Tensor | None = None,
-             escale: float = 1.0):
+             escale: float = 1.0, eidx: torch.Tensor | None = None,
+             wstride: int = 0, oscale: torch.Tensor | None = None):
     """y[N] = W4[N,K] @ stage(x): MXFP4 weights (Wq: N x K/2 packed
-    bytes, We: N x K/32 e8m0 scale bytes) — half the fp8 stream."""
+    bytes, We: N x K/32 e8m0 scale bytes) — half the fp8 stream.
+    eidx/wstride/oscale: MoE expert indexing as ``gemv_fp8`` — Wq and We
+    are the FIRST expert's rows of the stacked tensors, both offset by
+    the device int32 *eidx times ``wstride`` ELEMENTS (a multiple of
+    32), output scaled by *oscale before the residual."""
     N = Wq.shape[0]
     K = Wq.shape[1] * 2
+    if eidx is not None and (wstride < N * K or wstride % 32):
+        raise ValueError(f"gemv_fp4: wstride={wstride} elements must be a "
+                         f"multiple of 32 and cover the {N}x{K} expert")
     out_f32 = 1 if y.dtype == torch.float32 else 0
     _check(lib().launch_gemv_fp4(
         _ptr(Wq), _ptr(We), _ptr(x), _ptr(x2), _ptr(g), _ptr(g2),
         _ptr(y), _ptr(res), N, K, stage, act, ctypes.c_float(eps), out_f32,
         ctypes.c_float(softcap), nt, rpw, maxblocks,
-        ctypes.c_float(escale), _stream()), "gemv_fp4")
+        ctypes.c_float(escale), _ptr(eidx), ctypes.c_long(wstride),
+        _ptr(oscale), _stream()), "gemv_fp4")
 
 
 def gemm_fp8(xq: torch.Tensor, sx: torch.Tensor, Wq: torch.Tensor,
@@ -1602,6 +1616,88 @@ def moe_gemm_fp8_down(actq: torch.Tensor, sa: torch.Tensor,
     _moe_buf(name, "y", y, torch.float32, M * topk * H)
     _check(lib().launch_moe_gemm_fp8_down(
         _ptr(actq), _ptr(sa), _ptr(wdown_q_all), _ptr(wdown_s_all),
+        _ptr(tiles), _ptr(y), M, topk, E, H, I, tm, _stream()), name)
+
+
+def _moe_fp4_operands(name, a, sa, rows, w4, e4):
+    """Common checks of an e4m3 A [>= rows, K] with per-row fp32 scales
+    against MXFP4 weights w4 [N, K/2] + e4 [N, K/32]; returns K."""
+    for what, t in (("activations", a), ("packed weights", w4),
+                    ("block scales", e4)):
+        if (t.dim() != 2 or t.dtype != torch.uint8 or not t.is_cuda
+                or not t.is_contiguous()):
+            raise ValueError(f"{name}: {what} must be contiguous 2-D uint8 "
+                             f"on the GPU")
+    K = a.shape[1]
+    if K % 64 != 0 or w4.shape[1] * 2 != K:
+        raise ValueError(f"{name}: K={K} must be a multiple of 64 and match "
+                         f"the packed weights {tuple(w4.shape)} (K/2 bytes)")
+    if tuple(e4.shape) != (w4.shape[0], K // 32):
+        raise ValueError(f"{name}: block scales {tuple(e4.shape)} do not "
+                         f"cover {w4.shape[0]} weight rows x {K // 32} "
+                         f"blocks")
+    if a.shape[0] < rows:
+        raise ValueError(f"{name}: activations have {a.shape[0]} rows < "
+                         f"{rows}")
+    _moe_buf(name, "activation scales", sa, torch.float32, rows)
+    return K
+
+
+def moe_gemm_fp4_glu(xq: torch.Tensor, sx: torch.Tensor,
+                     slot_row: torch.Tensor, wgu_q4_all: torch.Tensor,
+                     wgu_e4_all: torch.Tensor, tiles: torch.Tensor,
+                     act_out: torch.Tensor, M: int, topk: int, tm: int,
+                     act: int = 0):
+    """``moe_gemm_glu`` on e4m3 rows x MXFP4 experts (scaled fp8 x fp4
+    MFMA, the block scales inside it): g/u = (xq[slot_row[s]] @ W4^T) *
+    sx[slot_row[s]], each rounded to bf16, act_out[s] = act(g) * u in
+    bf16.  xq [>= M, H] uint8 with sx [>= M] fp32 (one ``quant_fp8``);
+    wgu_q4_all [E*2I, H/2] uint8, per expert [gate; up], wgu_e4_all
+    [E*2I, H/32] uint8 (``quant_fp4``)."""
+    name = "moe_gemm_fp4_glu"
+    H = _moe_fp4_operands(name, xq, sx, M, wgu_q4_all, wgu_e4_all)
+    if act_out.dim() != 2:
+        raise ValueError(f"{name}: act_out must be [slots, I]")
+    I = act_out.shape[1]
+    if I < 64 or wgu_q4_all.shape[0] % (2 * I) != 0:
+        raise ValueError(f"{name}: wgu_q4_all rows {wgu_q4_all.shape[0]} "
+                         f"are not E blocks of 2*I, I={I} >= 64")
+    E = wgu_q4_all.shape[0] // (2 * I)
+    _moe_dims(name, M, topk, E, tm)
+    _moe_buf(name, "slot_row", slot_row, torch.int32, M * topk)
+    _moe_buf(name, "tiles", tiles, torch.int32,
+             1 + 3 * moe_max_tiles(M, topk, E, tm))
+    _moe_buf(name, "act_out", act_out, torch.bfloat16, M * topk * I)
+    _check(lib().launch_moe_gemm_fp4_glu(
+        _ptr(xq), _ptr(sx), _ptr(slot_row), _ptr(wgu_q4_all),
+        _ptr(wgu_e4_all), _ptr(tiles), _ptr(act_out), M, topk, E, H, I, act,
+        tm, _stream()), name)
+
+
+def moe_gemm_fp4_down(actq: torch.Tensor, sa: torch.Tensor,
+                      wdown_q4_all: torch.Tensor, wdown_e4_all: torch.Tensor,
+                      tiles: torch.Tensor, y: torch.Tensor, M: int,
+                      topk: int, tm: int):
+    """``moe_gemm_down`` on e4m3 rows x MXFP4 experts: y[s, :H] (fp32) =
+    (actq[s] @ Wd4[e(s)]^T) * sa[s].  actq [>= M*topk, I] uint8 in slot
+    order with sa [>= M*topk] fp32 (``quant_fp8`` of the GLU output);
+    wdown_q4_all [E*H, I/2] uint8, wdown_e4_all [E*H, I/32] uint8."""
+    name = "moe_gemm_fp4_down"
+    if y.dim() != 2:
+        raise ValueError(f"{name}: y must be [slots, H]")
+    I = _moe_fp4_operands(name, actq, sa, M * topk, wdown_q4_all,
+                          wdown_e4_all)
+    H = y.shape[1]
+    if H < 64 or H % 4 != 0 or wdown_q4_all.shape[0] % H != 0:
+        raise ValueError(f"{name}: wdown_q4_all rows {wdown_q4_all.shape[0]} "
+                         f"are not E blocks of H={H}")
+    E = wdown_q4_all.shape[0] // H
+    _moe_dims(name, M, topk, E, tm)
+    _moe_buf(name, "tiles", tiles, torch.int32,
+             1 + 3 * moe_max_tiles(M, topk, E, tm))
+    _moe_buf(name, "y", y, torch.float32, M * topk * H)
+    _check(lib().launch_moe_gemm_fp4_down(
+        _ptr(actq), _ptr(sa), _ptr(wdown_q4_all), _ptr(wdown_e4_all),
         _ptr(tiles), _ptr(y), M, topk, E, H, I, tm, _stream()), name)
 
 
