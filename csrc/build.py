@@ -13,6 +13,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRCS = [
     os.path.join(ROOT, "csrc", "llm_ops.hip"),
+    os.path.join(ROOT, "csrc", "attn_verify.hip"),
     os.path.join(ROOT, "csrc", "xgmi_comm.hip"),
 ]
 DEPS = [os.path.join(ROOT, "csrc", "common.h")]

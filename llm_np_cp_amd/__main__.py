@@ -51,6 +51,10 @@ def main(argv=None):
                     help="draft weight dtype (default: same as --dtype)")
     ap.add_argument("--spec-k", type=int, default=4,
                     help="draft tokens per verify pass")
+    ap.add_argument("--spec-skinny", action="store_true",
+                    help="with --draft: the target's verify pass on the "
+                         "skinny GEMMs and the fused verify attention "
+                         "(LLM_SPEC_SKINNY=1)")
     ap.add_argument("--no-cache", action="store_true",
                     help="stateless re-prefill each step (debug mode, "
                          "reference use_cache=False path)")
@@ -63,6 +67,9 @@ def main(argv=None):
 
     import llm_np_cp_amd as L
 
+    if args.spec_skinny:
+        import os
+        os.environ["LLM_SPEC_SKINNY"] = "1"
     tok, model, cfg = L.load_model(args.model, backend=args.backend,
                                    dtype=args.dtype, max_seq=args.max_seq,
                                    kv_dtype=args.kv_dtype, lora=args.lora)

@@ -85,3 +85,19 @@ class RowState:
         """The same state narrowed to rows ``sl`` of every member."""
         return RowState(*(getattr(self, f.name)[sl]
                           for f in fields(self)[:-1]), sl=sl)
+
+
+@dataclass(frozen=True)
+class FusedRows:
+    """What the fused layer stack (``_batch_layers_fused``) works on
+    besides the residual stream: the row buffers, the device ids of the
+    embed gather, the logits, and the attention call
+    ``attn(layer, window, B)`` that reads ``qkv`` into ``b_att``."""
+    qkv: Any
+    gu: Any
+    t1: Any
+    t2: Any
+    hb: Any
+    ids: Any
+    logits: Any
+    attn: Any

@@ -32,7 +32,7 @@ from ..core.config import ModelConfig
 from ..ops import hip_ops as ho
 from ..parallel import tp as tpu
 from ..utils.tracing import trace_range
-from .decode_spec import RowState, SampleSpec
+from .decode_spec import FusedRows, RowState, SampleSpec
 
 
 class DeviceCacheHandle:
@@ -75,7 +75,8 @@ class GPUModel:
                  kv_dtype: str = "bf16", max_batch: int = 1,
                  batch_fp4: Optional[bool] = None,
                  batch_skinny: Optional[bool] = None,
-                 moe_grouped: Optional[bool] = None):
+                 moe_grouped: Optional[bool] = None,
+                 spec_skinny: Optional[bool] = None):
         """``max_seq=None`` sizes the KV pool from FREE HBM after the
         weights land (288 GB per MI355X — SURVEY §5 long-context), capped
         at config.max_position_embeddings.  ``max_batch>1`` allocates
@@ -96,7 +97,12 @@ class GPUModel:
         ignored for every other engine.  A ``dtype="fp4"`` MoE engine
         has no dense loop: it is single-copy MXFP4 whatever ``max_batch``
         is, and its rows always take the grouped path (scaled e4m3 x
-        e2m1 MFMA on the expert weights themselves)."""
+        e2m1 MFMA on the expert weights themselves).  ``spec_skinny``
+        (None = env LLM_SPEC_SKINNY, default off) runs the speculative
+        verify pass of up to 16 rows on the skinny GEMMs of the engine's
+        dtype and the fused verify attention (`ho.attn_verify`) instead
+        of the prefill path; honoured on single-GPU, non-MoE engines
+        with head_dim 64 / 128 / 256, ignored elsewhere."""
         if not torch.cuda.is_available():
             raise RuntimeError("GPUModel requires a GPU (MI355X)")
         self.config = config
@@ -139,6 +145,17 @@ class GPUModel:
         # do not apply
         self.moe_grouped = bool((moe_grouped or dtype == "fp4")
                                 and config.is_moe)
+        if spec_skinny is None:
+            import os as _os
+            spec_skinny = _os.environ.get("LLM_SPEC_SKINNY", "0").strip() \
+                not in ("", "0")
+        # the verify attention's head grouping: <= 4 query heads per wave
+        # (2 at head_dim 256)
+        _g = config.num_attention_heads // max(config.num_key_value_heads, 1)
+        self.spec_skinny = bool(
+            spec_skinny and not config.is_moe
+            and config.head_dim in (64, 128, 256)
+            and _g <= (8 if config.head_dim == 256 else 16))
         if kv_dtype not in ("bf16", "fp8"):
             raise ValueError(f"unsupported kv_dtype {kv_dtype!r}")
         self.kv_dtype = kv_dtype
@@ -154,6 +171,7 @@ class GPUModel:
         self.rank, self.world = tpu.init_distributed()
         self.batch_skinny = self.batch_skinny and self.world == 1
         self.moe_grouped = self.moe_grouped and self.world == 1
+        self.spec_skinny = self.spec_skinny and self.world == 1
         # exercise the TP code path on 1 GPU (collectives no-op at
         # world=1, partial sums are then exact) — used by tests
         self.tp_branch = self.world > 1 or force_tp_path
@@ -1211,6 +1229,23 @@ class GPUModel:
             self.sp_rec = torch.zeros(self.SPEC_REC, ho.SPEC_REC_WORDS,
                                       dtype=torch.int32, device=dev)
             self.sp_nrec = torch.zeros(1, dtype=torch.int32, device=dev)
+            if self.spec_skinny:
+                # the fused stack's row buffers for the verify pass (a
+                # speculative target usually has max_batch == 1 and no
+                # bt_* set) and the verify attention's chunk partials
+                R, H, I = ho.ATTN_VERIFY_MAX_ROWS, self.H, self.inter_l
+                bf = dict(dtype=torch.bfloat16, device=dev)
+                self.sp_qkv = torch.zeros(
+                    R, (self.nh_l + 2 * self.kvh_l) * self.hd, **bf)
+                self.sp_gu = torch.zeros(R, 2 * I, **bf)
+                self.sp_t1 = torch.zeros(R, H, **bf)
+                self.sp_t2 = torch.zeros(R, H, **bf)
+                self.sp_hb = torch.zeros(R, H, **bf)
+                self.sp_xs = torch.zeros(R, H, **bf)
+                self.sp_attn = torch.zeros(ho.attn_verify_scratch_words(
+                    R, self.nh_l, self.hd, self.max_seq,
+                    ho.attn_verify_chunk(self.max_seq)),
+                    dtype=torch.float32, device=dev)
 
     def decode_steps_async(self, n: int):
         """``n`` greedy decode steps with no synchronise and no ring
@@ -1251,6 +1286,51 @@ class GPUModel:
         M = k + 1
         ho.spec_stage(self.ids_buf, self.next_token,
                       draft.out_ring if k else self.out_ring, k)
+        y = self.sp_logits[:M]
+        if self.spec_skinny and M <= ho.ATTN_VERIFY_MAX_ROWS:
+            self._spec_layers_skinny(M)
+        else:
+            self._spec_layers_prefill(M)
+        if k == 0:
+            self._sample_tail(y, self._sv, 1, SampleSpec())
+            return
+        ho.spec_verify(y, k, self.ids_buf[1:1 + k], self.sp_scratch,
+                       self.len_buf, self.next_token, self.out_ring,
+                       self.nout, draft.len_buf, draft.next_token,
+                       draft.nout, self.sp_rec, self.sp_nrec, blocks=blocks)
+
+    def _spec_layers_skinny(self, M: int):
+        """The verify pass's M <= 16 rows through the fused stack of the
+        lockstep step (`_batch_layers_fused`) on the skinny GEMM of the
+        engine's dtype, each weight streamed once: a row set of its own,
+        ``ids_buf`` as the embed-gather ids, `ho.attn_verify` on the
+        sequence's pool from ``len_buf`` as the attention, the lm_head
+        (final softcap in its epilogue) into ``sp_logits``.  An fp4
+        engine runs on its MXFP4 weights, or on the fp8 copy where it
+        keeps one."""
+        rows = FusedRows(self.sp_qkv, self.sp_gu, self.sp_t1, self.sp_t2,
+                         self.sp_hb, self.ids_buf, self.sp_logits,
+                         self._attn_verify_rows)
+        if not self.fp8:
+            self._batch_layers_fused(
+                M, partial(self._proj_skinny_bf16, M, xs=self.sp_xs),
+                sfx=("", ""), glu_epilogue=True, rows=rows)
+        elif self.keep_fp8:
+            self._batch_layers_fused(M, partial(self._proj_skinny, M),
+                                     rows=rows)
+        else:
+            self._batch_layers_fused(M, partial(self._proj_skinny4, M),
+                                     sfx=("_q4", "_e4"), rows=rows)
+
+    def _attn_verify_rows(self, i: int, window: int, M: int):
+        ho.attn_verify(self.sp_qkv, self._kc(i), self._vc(i), self.b_att,
+                       self.len_buf, self.cos_t, self.sin_t, self.sp_attn,
+                       M, self.nh_l, self.kvh_l, self.hd, self.scale,
+                       softcap=self.attn_softcap, window=window,
+                       kS=self._ks(i), vS=self._vs(i))
+
+    def _spec_layers_prefill(self, M: int):
+        """The verify pass's rows through the prefill path."""
         ho.embed(self.embed, self.ids_buf, self.b_h, M,
                  self.config.embed_scale)
         self._layers_forward(M)
@@ -1269,13 +1349,6 @@ class GPUModel:
             ho.gemm(self.b_xn[:M], self.lm_head, y, accbuf=self.b_gemm_acc)
         if self.final_softcap:
             ho.softcap(y, self.final_softcap)
-        if k == 0:
-            self._sample_tail(y, self._sv, 1, SampleSpec())
-            return
-        ho.spec_verify(y, k, self.ids_buf[1:1 + k], self.sp_scratch,
-                       self.len_buf, self.next_token, self.out_ring,
-                       self.nout, draft.len_buf, draft.next_token,
-                       draft.nout, self.sp_rec, self.sp_nrec, blocks=blocks)
 
     def spec_chunk(self, draft: "GPUModel", k: int, cycles: int,
                    nout0: int):
@@ -2051,21 +2124,32 @@ class GPUModel:
                            softcap=softcap, accbuf=self.b_gemm_acc)
 
     def _proj_skinny_bf16(self, B, w, _w, x, xstride, y, K, N, *, res=None,
-                          bias=None, softcap=0.0, glu=0, act=0, **stage_kw):
+                          bias=None, softcap=0.0, glu=0, act=0, xs=None,
+                          **stage_kw):
         """The same projection on the bf16 weights: a norm stage writes
         bf16 rows (`stage_rows`) for the skinny bf16 MFMA GEMM, a RAW
         input is read by the GEMM in place.  ``glu`` = I: the GLU is the
         GEMM's epilogue, y[:, :I] of the [B, N = 2I] buffer."""
         if stage_kw:
-            ho.stage_rows(x, xstride, self.bt_xs, B, K, **stage_kw)
-            x, xstride = self.bt_xs, K
+            xs = self.bt_xs if xs is None else xs
+            ho.stage_rows(x, xstride, xs, B, K, **stage_kw)
+            x, xstride = xs, K
         ho.gemm_bf16_skinny(x, xstride, w, y, B, N, res=res,
                             rstride=N if res is not None else 0, bias=bias,
                             softcap=softcap, glu=glu, act=act,
                             accbuf=self.b_gemm_acc)
 
+    def _attn_dec_rows(self, i: int, window: int, B: int):
+        ho.attn_dec(self.bt_qkv, self.k_cache[i], self.v_cache[i],
+                    self.b_att[0], self.bt_lens, self.cos_t, self.sin_t,
+                    self.bt_scratch, self.bt_attn_cnt,
+                    self.nh_l, self.kvh_l, self.hd, self.scale,
+                    softcap=self.attn_softcap, window=window,
+                    split=self.attn_split, kS=self.k_scale[i],
+                    vS=self.v_scale[i], batch=B, merge=self.attn_merge)
+
     def _batch_layers_fused(self, B: int, proj, sfx=("_q", "_s"),
-                            glu_epilogue=False):
+                            glu_epilogue=False, rows=None):
         """Fused lockstep layer stack (fp8 / MXFP4): mirrors
         `_decode_layers`' 4-5 projections per layer over B rows, each one
         ``proj(wq, ws, x, xstride, y, K, N, res=, bias=, softcap=,
@@ -2075,14 +2159,22 @@ class GPUModel:
         copy, ("_q4", "_e4") the MXFP4 one, ("", "") the bf16 tensor
         (twice).  ``glu_epilogue``: the wgu ``proj`` applies the GLU
         itself (``glu=I, act=``, result in gu[:, :I]) and wdown reads
-        those rows RAW; otherwise the GLU is wdown's staging op."""
+        those rows RAW; otherwise the GLU is wdown's staging op.
+        ``rows`` (`FusedRows`): the row buffers, the embed-gather ids,
+        the logits and the attention call ``attn(layer, window, B)``
+        that reads ``rows.qkv`` into ``b_att``; default the lockstep
+        rows' ``bt_*`` set with `ho.attn_dec`."""
+        if rows is None:
+            rows = FusedRows(self.bt_qkv, self.bt_gu, self.bt_t1, self.bt_t2,
+                             self.bt_hb, self.bt_next, self.bt_logits,
+                             self._attn_dec_rows)
         qs, ss = sfx
         cfg = self.config
         eps = cfg.rms_norm_eps
         H, I = self.H, self.inter_l
         h = self.b_h            # (PC, H): rows 0..B = per-seq h
-        hb = self.bt_hb         # gemma ping-pong
-        t1, t2, gu = self.bt_t1, self.bt_t2, self.bt_gu
+        hb = rows.hb            # gemma ping-pong
+        t1, t2, gu = rows.t1, rows.t2, rows.gu
         qkvw = (self.nh_l + 2 * self.kvh_l) * self.hd
         nhh = self.nh_l * self.hd
         glu = dict(stage=ho.STAGE_GLU, x2=gu[:, I:], x2stride=2 * I,
@@ -2106,21 +2198,15 @@ class GPUModel:
             elif i == 0:
                 # embed gather fused into the QKV staging pass
                 x, xstride = self.embed, 0
-                st = dict(stage=ho.STAGE_NORM_EMBED, x2=self.bt_next,
+                st = dict(stage=ho.STAGE_NORM_EMBED, x2=rows.ids,
                           g=lw["g_in"], hout=h, hstride=H, eps=eps,
                           escale=cfg.embed_scale)
             else:
                 st = dict(stage=ho.STAGE_NORM, g=lw["g_in"], eps=eps)
-            proj(lw["wqkv" + qs], lw["wqkv" + ss], x, xstride, self.bt_qkv,
+            proj(lw["wqkv" + qs], lw["wqkv" + ss], x, xstride, rows.qkv,
                  H, qkvw, bias=lw.get("bqkv"), **st)
             prev = lw
-            ho.attn_dec(self.bt_qkv, self.k_cache[i], self.v_cache[i],
-                        self.b_att[0], self.bt_lens, self.cos_t, self.sin_t,
-                        self.bt_scratch, self.bt_attn_cnt,
-                        self.nh_l, self.kvh_l, self.hd, self.scale,
-                        softcap=self.attn_softcap, window=window or 0,
-                        split=self.attn_split, kS=self.k_scale[i],
-                        vS=self.v_scale[i], batch=B, merge=self.attn_merge)
+            rows.attn(i, window or 0, B)
             if self.gemma:
                 proj(lw["wo" + qs], lw["wo" + ss], self.b_att, nhh, t1, nhh,
                      H)
@@ -2141,7 +2227,7 @@ class GPUModel:
         else:
             x, st = h, dict(stage=ho.STAGE_NORM, g=self.g_final, eps=eps)
         proj(getattr(self, "lm_head" + qs), getattr(self, "lm_head" + ss),
-             x, H, self.bt_logits, H, self.vocab_l,
+             x, H, rows.logits, H, self.vocab_l,
              softcap=self.final_softcap, **st)
 
     def prefill_batch(self, prompts) -> None:

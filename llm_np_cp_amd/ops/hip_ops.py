@@ -46,6 +46,10 @@ _SIGS = {
     "launch_attn_prefill_mfma": [ctypes.c_void_p] * 7 + [ctypes.c_int] * 6 +
                                 [ctypes.c_float, ctypes.c_float,
                                  ctypes.c_int, ctypes.c_void_p],
+    "launch_attn_verify": [ctypes.c_void_p] * 5 + [ctypes.c_int] +
+                          [ctypes.c_void_p] * 5 + [ctypes.c_int] * 6 +
+                          [ctypes.c_float, ctypes.c_float, ctypes.c_int,
+                           ctypes.c_void_p],
     "launch_attn_dec": [ctypes.c_void_p] * 9 + [ctypes.c_int] +
                        [ctypes.c_void_p] * 2 + [ctypes.c_int] * 6 +
                        [ctypes.c_float, ctypes.c_float, ctypes.c_int,
@@ -353,6 +357,73 @@ def attn_prefill_mfma(q: torch.Tensor, k_cache: torch.Tensor,
         _ptr(kS), _ptr(vS), 1 if kS is not None else 0,
         M, nh, kvh, hd, S, ctypes.c_float(scale), ctypes.c_float(softcap),
         window, _stream()), "attn_prefill_mfma")
+
+
+ATTN_VERIFY_MAX_ROWS = 16
+
+
+def attn_verify_chunk(S: int) -> int:
+    """KV chunk of ``attn_verify`` for a pool of capacity S: a multiple
+    of 16, at least 32, such that the pool has at most 64 chunks.  A
+    function of S alone: the bits of an output row depend on it."""
+    return max(32, 16 * -(-S // (64 * 16)))
+
+
+def attn_verify_scratch_words(R: int, nh: int, hd: int, S: int,
+                              chunk: int) -> int:
+    """fp32 words of chunk partials ``attn_verify`` needs."""
+    return -(-S // chunk) * nh * R * (hd + 4)
+
+
+def attn_verify(qkv: torch.Tensor, k_cache: torch.Tensor,
+                v_cache: torch.Tensor, out: torch.Tensor,
+                len_ptr: torch.Tensor, cos_t: torch.Tensor,
+                sin_t: torch.Tensor, scratch: torch.Tensor, R: int,
+                nh: int, kvh: int, hd: int, scale: float,
+                softcap: float = 0.0, window: int = 0, chunk: int = 0,
+                kS: torch.Tensor | None = None,
+                vS: torch.Tensor | None = None):
+    """Fused multi-row causal decode attention (`k_attn_verify` + merge):
+    qkv [R, (nh + 2 kvh) hd] bf16 holds R = 1..16 consecutive new rows of
+    ONE sequence, biased, not yet roped; row r sits at position
+    *len_ptr + r.  Ropes q and k, writes the R new K/V rows into the pool
+    [kvh, S, hd] (the bits of ``rope_cache``; kS/vS given => e4m3 pool
+    with per-(head, pos) scales) and writes out [R, nh hd] bf16: each row
+    attends the history and the new rows up to itself (``window``,
+    ``softcap`` as in ``attn_prefill_mfma``).  ``chunk`` (0 =
+    ``attn_verify_chunk(S)``): KV positions per block, a multiple of 16.
+    ``scratch``: fp32, >= ``attn_verify_scratch_words``.  ``len_ptr`` is
+    read on the device and never written; the caller guarantees
+    *len_ptr + R <= S."""
+    S = k_cache.shape[-2]
+    if hd not in (64, 128, 256):
+        raise ValueError(f"attn_verify: head_dim {hd} not in (64, 128, 256)")
+    if not 1 <= R <= ATTN_VERIFY_MAX_ROWS:
+        raise ValueError(f"attn_verify: R={R} outside 1.."
+                         f"{ATTN_VERIFY_MAX_ROWS}")
+    if kvh < 1 or nh % kvh or nh // kvh > (8 if hd == 256 else 16):
+        raise ValueError(f"attn_verify: nh={nh}, kvh={kvh} at hd={hd}: "
+                         f"unsupported head grouping")
+    chunk = chunk or attn_verify_chunk(S)
+    if chunk < 16 or chunk % 16:
+        raise ValueError(f"attn_verify: chunk={chunk} is not a positive "
+                         f"multiple of 16")
+    need = attn_verify_scratch_words(R, nh, hd, S, chunk)
+    if scratch.dtype != torch.float32 or scratch.numel() < need:
+        raise ValueError(f"attn_verify: scratch has {scratch.numel()} "
+                         f"{scratch.dtype} words, needs {need} fp32")
+    if qkv.numel() < R * (nh + 2 * kvh) * hd or out.numel() < R * nh * hd:
+        raise ValueError("attn_verify: qkv / out smaller than R rows")
+    if (kS is None) != (vS is None) or \
+            k_cache.element_size() != (2 if kS is None else 1):
+        raise ValueError("attn_verify: bf16 pool without scales, or e4m3 "
+                         "pool with kS and vS")
+    _check(lib().launch_attn_verify(
+        _ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(kS), _ptr(vS),
+        1 if kS is not None else 0, _ptr(cos_t), _ptr(sin_t), _ptr(len_ptr),
+        _ptr(out), _ptr(scratch), R, nh, kvh, hd, S, chunk,
+        ctypes.c_float(scale), ctypes.c_float(softcap), window, _stream()),
+        "attn_verify")
 
 
 ATTN_MERGE = {"auto": 0, "ticket": 1, "block": 2}

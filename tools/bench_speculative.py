@@ -80,6 +80,9 @@ def main():
                     help="also sweep SPEC_CHUNK over these values (k = 4, "
                          "first set-up)")
     ap.add_argument("--prompt", default="Once upon a time")
+    ap.add_argument("--spec-skinny", action="store_true",
+                    help="target verify pass on the skinny GEMMs and "
+                         "attn_verify (LLM_SPEC_SKINNY=1)")
     ap.add_argument("--kernel-only", action="store_true")
     ap.add_argument("--kernel-iters", type=int, default=200)
     args = ap.parse_args()
@@ -96,6 +99,8 @@ def main():
         return
 
     dname = args.draft or args.target
+    if args.spec_skinny:
+        os.environ["LLM_SPEC_SKINNY"] = "1"
     tok, target, _ = L.load_model(args.target, backend="gpu",
                                   dtype=args.dtype, max_seq=args.max_seq,
                                   seed=0)
