@@ -14,6 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRCS = [
     os.path.join(ROOT, "csrc", "llm_ops.hip"),
     os.path.join(ROOT, "csrc", "attn_verify.hip"),
+    os.path.join(ROOT, "csrc", "spec_sample.hip"),
     os.path.join(ROOT, "csrc", "xgmi_comm.hip"),
 ]
 DEPS = [os.path.join(ROOT, "csrc", "common.h")]

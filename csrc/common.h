@@ -55,3 +55,34 @@ DEVINL unsigned long long f32x8_to_fp8(const float* f, float rs) {
   hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6] * rs, f[7] * rs, hi, true);
   return (unsigned long long)lo | ((unsigned long long)hi << 32);
 }
+
+// ---- sampler / speculative helpers shared by llm_ops.hip and
+// spec_sample.hip ----
+DEVINL uint32_t hash32(uint32_t x) {
+  x ^= x >> 16; x *= 0x7feb352du;
+  x ^= x >> 15; x *= 0x846ca68bu;
+  x ^= x >> 16;
+  return x;
+}
+
+// order-preserving float->u32 key (monotone for max); invertible
+DEVINL uint32_t fkey(float f) {
+  union { float f; uint32_t u; } c; c.f = f;
+  return (c.u & 0x80000000u) ? ~c.u : (c.u ^ 0x80000000u);
+}
+DEVINL float fkey_inv(uint32_t k) {
+  union { float f; uint32_t u; } c;
+  c.u = (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k;
+  return c.f;
+}
+
+// pack (key, idx): ties prefer the SMALLEST index (matches np.argmax)
+DEVINL uint64_t pack_ki(uint32_t key, int idx) {
+  return ((uint64_t)key << 32) | (uint32_t)(0x7fffffff - idx);
+}
+DEVINL int unpack_idx(uint64_t p) { return 0x7fffffff - (int)(uint32_t)p; }
+
+// speculative decoding: most drafts per verify pass, int32 words of one
+// record {m, drafts[SPEC_MAX_K]}
+#define SPEC_MAX_K 16
+#define SPEC_REC_WORDS (SPEC_MAX_K + 1)

@@ -3359,30 +3359,6 @@ extern "C" hipError_t launch_embed(const void* embed, const void* ids,
 // whole decode step is graph-replayable.
 // ====================================================================
 
-DEVINL uint32_t hash32(uint32_t x) {
-  x ^= x >> 16; x *= 0x7feb352du;
-  x ^= x >> 15; x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
-
-// order-preserving float->u32 key (monotone for max); invertible
-DEVINL uint32_t fkey(float f) {
-  union { float f; uint32_t u; } c; c.f = f;
-  return (c.u & 0x80000000u) ? ~c.u : (c.u ^ 0x80000000u);
-}
-DEVINL float fkey_inv(uint32_t k) {
-  union { float f; uint32_t u; } c;
-  c.u = (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k;
-  return c.f;
-}
-
-// pack (key, idx): ties prefer the SMALLEST index (matches np.argmax)
-DEVINL uint64_t pack_ki(uint32_t key, int idx) {
-  return ((uint64_t)key << 32) | (uint32_t)(0x7fffffff - idx);
-}
-DEVINL int unpack_idx(uint64_t p) { return 0x7fffffff - (int)(uint32_t)p; }
-
 // pass 1 (min-p only): global max logit -> gmax[b] (packed).
 // Batched: grid.y = sequence row b (lbf16: logits stored bf16 — the
 // batched lm_head GEMM path emits bf16 rows).
@@ -4765,9 +4741,8 @@ extern "C" hipError_t launch_logprob_rows(const void* logits, int V,
 // m <= k by construction, so no length above n + k + 1 is ever written;
 // ring writes past ring_cap are dropped.  Plain stores only.
 // ====================================================================
-#define SPEC_MAX_K 16
+// SPEC_MAX_K, SPEC_REC_WORDS: common.h (shared with spec_sample.hip)
 #define SPEC_SCRATCH_WORDS (SPEC_MAX_K + 2)
-#define SPEC_REC_WORDS (SPEC_MAX_K + 1)
 #define SPEC_AUTO_BLOCKS 8
 
 template <bool BF>

@@ -65,6 +65,20 @@ class SampleSpec:
 
 
 @dataclass(frozen=True)
+class SpecSampler:
+    """The sampler of a stochastic speculative run: the launch arguments
+    of ``hip_ops.spec_sample`` (the engines' sampled steps read the same
+    values from their sampler tables)."""
+    inv_temp: float
+    min_p: float
+    seed: int
+
+    # what a sampled step of such a run samples with: the per-row table,
+    # a min-p row (temperature = min-p with an empty cut)
+    step_spec = SampleSpec(rows=frozenset({SAMP_MIN_P}))
+
+
+@dataclass(frozen=True)
 class RowState:
     """Sampler state of a group of rows: table, scratch, the sampled
     token, the output ring with its count, and the sequence length."""

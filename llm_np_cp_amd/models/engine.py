@@ -32,7 +32,7 @@ from ..core.config import ModelConfig
 from ..ops import hip_ops as ho
 from ..parallel import tp as tpu
 from ..utils.tracing import trace_range
-from .decode_spec import FusedRows, RowState, SampleSpec
+from .decode_spec import FusedRows, RowState, SampleSpec, SpecSampler
 
 
 class DeviceCacheHandle:
@@ -64,6 +64,10 @@ class GPUModel:
     # target or draft (``speculative_tokens``; set per instance: True at
     # world == 1 without MoE)
     device_speculative = False
+    # ... and stochastic (temperature / min-p) speculative sampling too,
+    # with this engine as the target (``spec_sample=True``; needs
+    # ``device_speculative``)
+    device_speculative_sampling = False
     # verify cycles a speculative chunk runs between two host reads
     # (profiles/spec_device.md)
     SPEC_CHUNK = 4
@@ -76,7 +80,8 @@ class GPUModel:
                  batch_fp4: Optional[bool] = None,
                  batch_skinny: Optional[bool] = None,
                  moe_grouped: Optional[bool] = None,
-                 spec_skinny: Optional[bool] = None):
+                 spec_skinny: Optional[bool] = None,
+                 spec_sample: Optional[bool] = None):
         """``max_seq=None`` sizes the KV pool from FREE HBM after the
         weights land (288 GB per MI355X — SURVEY §5 long-context), capped
         at config.max_position_embeddings.  ``max_batch>1`` allocates
@@ -102,7 +107,12 @@ class GPUModel:
         verify pass of up to 16 rows on the skinny GEMMs of the engine's
         dtype and the fused verify attention (`ho.attn_verify`) instead
         of the prefill path; honoured on single-GPU, non-MoE engines
-        with head_dim 64 / 128 / 256, ignored elsewhere."""
+        with head_dim 64 / 128 / 256, ignored elsewhere.  ``spec_sample``
+        (None = env LLM_SPEC_SAMPLE, default off) lets this engine, as
+        the target, run ``temperature`` / ``min_p`` speculative decoding
+        device-side (`ho.spec_sample`: accept / reject, residual draw and
+        commit on the GPU); honoured where ``device_speculative`` holds,
+        ignored elsewhere."""
         if not torch.cuda.is_available():
             raise RuntimeError("GPUModel requires a GPU (MI355X)")
         self.config = config
@@ -206,6 +216,15 @@ class GPUModel:
         # allocated by the first verify pass
         self.device_speculative = self.world == 1 and not self.moe
         self.sp_logits = self.sp_scratch = self.sp_rec = self.sp_nrec = None
+        if spec_sample is None:
+            import os as _os
+            spec_sample = _os.environ.get("LLM_SPEC_SAMPLE", "0").strip() \
+                not in ("", "0")
+        self.device_speculative_sampling = bool(
+            spec_sample and self.device_speculative)
+        # stochastic verify state (scratch / partial masses / draw counter)
+        # and, on a draft, the kept fp32 rows of its sampled steps
+        self.ss_scratch = self.ss_part = self.ss_ctr = self.sp_keep = None
         if self.world == 1:
             self.device_row_sampler = True
         # host mirror of the per-row sampler table: slot -> mode of every
@@ -1246,13 +1265,71 @@ class GPUModel:
                     R, self.nh_l, self.hd, self.max_seq,
                     ho.attn_verify_chunk(self.max_seq)),
                     dtype=torch.float32, device=dev)
+        if self.device_speculative_sampling and self.ss_scratch is None:
+            dev = self.device
+            self.ss_scratch = torch.zeros(ho.SPEC_SAMPLE_SCRATCH_WORDS,
+                                          dtype=torch.int64, device=dev)
+            self.ss_part = torch.zeros(
+                ho.spec_sample_part_words(self.config.vocab_size),
+                dtype=torch.float32, device=dev)
+            self.ss_ctr = torch.zeros(1, dtype=torch.int64, device=dev)
 
-    def decode_steps_async(self, n: int):
+    # what the draft's seed differs from the request's by: the target draws
+    # its own tokens (first token, plain steps) from the request's seed with
+    # the same sampler kernels, and the draft's stream must not repeat them
+    _SPEC_DRAFT_SEED = 0xD6E8FEB86659FD93
+
+    def _spec_sampler(self, draft: "GPUModel", params) -> SpecSampler:
+        """Set up a stochastic speculative run: ``params`` (a
+        ``SamplingParams`` or a ``row_sampler`` dict; ``temperature`` /
+        ``min_p``) packed into this engine's and the draft's
+        single-sequence sampler rows (draw counters 0, the draft under a
+        seed derived from the request's), the path's own draw counter back
+        to 0, the draft's kept rows allocated.  Same seed, same tokens; a
+        request without a seed gets one as in ``generate_tokens``."""
+        if not self.device_speculative_sampling:
+            raise ValueError("this engine was not built with "
+                             "spec_sample=True")
+        if not isinstance(params, dict):
+            from ..runtime.sampling import device_row_sampler_kwargs
+            params = device_row_sampler_kwargs(params)
+        words, mode = self._samp_pack(params)
+        if mode != ho.SAMP_MIN_P:
+            raise ValueError("device-side speculative sampling serves the "
+                             "temperature and min_p strategies")
+        w = words.numpy().view(np.uint32)
+        inv_temp, min_p = (float(x) for x in w[1:3].view(np.float32))
+        seed = int(w[5]) | (int(w[6]) << 32)
+        dw = w.copy()
+        dseed = seed ^ self._SPEC_DRAFT_SEED
+        dw[5], dw[6] = dseed & 0xFFFFFFFF, dseed >> 32
+        self._spec_alloc()
+        self.s_samp[0].copy_(words)
+        draft.s_samp[0].copy_(torch.from_numpy(dw.view(np.int32)))
+        self.ss_ctr.zero_()
+        if draft.sp_keep is None:
+            draft.sp_keep = torch.zeros(
+                ho.SPEC_MAX_K + 1, draft.config.vocab_size,
+                dtype=torch.float32, device=draft.device)
+        return SpecSampler(inv_temp, min_p, seed)
+
+    def _step_keep(self, spec: SampleSpec):
+        """A sampled draft step that keeps the row its token was drawn
+        from (``sp_keep[nout - 1]``) for the target's ``spec_sample``."""
+        self._step(spec)
+        ho.spec_keep(self.b_logits, self.sp_keep, self.nout)
+
+    def decode_steps_async(self, n: int,
+                           sampler: Optional[SpecSampler] = None):
         """``n`` greedy decode steps with no synchronise and no ring
         read-back: replays of the greedy decode graph (captured here when
         it is not there yet; its warm-up is one REAL step and counts as
         one of the n), or eager steps when capture failed.  The
-        speculative draft loop; ``decode`` keeps its behaviour."""
+        speculative draft loop; ``decode`` keeps its behaviour.
+        ``sampler``: SAMPLED steps instead, through the single-sequence
+        sampler row (``_spec_sampler`` wrote it; its values are device
+        data), each followed by ``spec_keep``; their graph is keyed on the
+        rows key plus ``"keep"`` and on no value."""
         if n < 1:
             return
         if self._host_len + n > self.max_seq:
@@ -1260,18 +1337,33 @@ class GPUModel:
                 f"decode would overflow the KV pool: len {self._host_len} "
                 f"+ {n} > max_seq {self.max_seq}")
         self._host_len += n
-        taken, ok = self.capture_decode_graph()
+        if sampler is None:
+            spec = SampleSpec()
+            step = partial(self._step, spec)
+            taken, ok = self.capture_decode_graph()
+        else:
+            spec = sampler.step_spec
+            step = partial(self._step_keep, spec)
+            mode = spec.graph_key("decode") + ("keep",)
+            taken, ok = 0, self._graph_mode == mode
+            if not ok and not self._graph_failed:
+                taken = 1
+                g = self._warm_and_capture(step)
+                if g is None:
+                    torch.cuda.synchronize()
+                else:
+                    self._graph, self._graph_mode, ok = g, mode, True
         n -= taken
         if ok:
             for _ in range(n):
                 self._graph.replay()
         else:
-            spec = SampleSpec()
             for _ in range(n):
-                self._step(spec)
+                step()
 
     def spec_verify_pass(self, draft: Optional["GPUModel"], k: int,
-                         blocks: int = 0):
+                         blocks: int = 0,
+                         sampler: Optional[SpecSampler] = None):
         """One verify pass of greedy speculative decoding on this engine,
         nothing crossing to the host: stage [next_token, draft.out_ring[:k]]
         into ids_buf, embed, the layer stack over k+1 rows from len_buf,
@@ -1281,7 +1373,9 @@ class GPUModel:
         state (docs/KERNELS.md).  ``k`` = 0 is a plain greedy step through
         the same kernels (``draft`` unused, may be None): the sampling
         tail commits row 0.  The caller guarantees len + k + 1 <= max_seq
-        on both engines."""
+        on both engines.  ``sampler``: the stochastic pass — it ends in
+        ``spec_sample`` on the draft's kept rows instead (``k`` = 0: the
+        sampling tail with the sampler row)."""
         self._spec_alloc()
         M = k + 1
         ho.spec_stage(self.ids_buf, self.next_token,
@@ -1292,7 +1386,17 @@ class GPUModel:
         else:
             self._spec_layers_prefill(M)
         if k == 0:
-            self._sample_tail(y, self._sv, 1, SampleSpec())
+            self._sample_tail(y, self._sv, 1,
+                              sampler.step_spec if sampler else SampleSpec())
+            return
+        if sampler is not None:
+            ho.spec_sample(y, draft.sp_keep, k, self.ids_buf[1:1 + k],
+                           sampler.inv_temp, sampler.min_p, sampler.seed,
+                           self.ss_ctr, self.ss_scratch, self.ss_part,
+                           self.len_buf, self.next_token, self.out_ring,
+                           self.nout, draft.len_buf, draft.next_token,
+                           draft.nout, self.sp_rec, self.sp_nrec,
+                           blocks=blocks)
             return
         ho.spec_verify(y, k, self.ids_buf[1:1 + k], self.sp_scratch,
                        self.len_buf, self.next_token, self.out_ring,
@@ -1351,7 +1455,7 @@ class GPUModel:
             ho.softcap(y, self.final_softcap)
 
     def spec_chunk(self, draft: "GPUModel", k: int, cycles: int,
-                   nout0: int):
+                   nout0: int, sampler: Optional[SpecSampler] = None):
         """``cycles`` speculative cycles back to back, ONE synchronise at
         the end.  A cycle: k+1 draft steps (the last one writes the KV of
         the k-th proposal, so a fully accepted cycle leaves the draft
@@ -1361,7 +1465,8 @@ class GPUModel:
         ``(ids, recs)``: the tokens emitted (int32 array) and, for k > 0,
         one ``(m, drafts)`` per cycle; both engines' ``_host_len`` mirror
         the device lengths afterwards.  The caller has checked that
-        len + cycles * (k+1) fits both pools."""
+        len + cycles * (k+1) fits both pools.  ``sampler``: the cycles of
+        a stochastic run (sampled draft steps, ``spec_sample``)."""
         n = self._host_len
         need = n + cycles * (k + 1)
         if need > self.max_seq or (k and need > draft.max_seq):
@@ -1375,8 +1480,8 @@ class GPUModel:
             draft._host_len = n
         for _ in range(cycles):
             if k:
-                draft.decode_steps_async(k + 1)
-            self.spec_verify_pass(draft, k)
+                draft.decode_steps_async(k + 1, sampler=sampler)
+            self.spec_verify_pass(draft, k, sampler=sampler)
         scal = torch.cat([self.nout, self.len_buf,
                           draft.len_buf if k else self.len_buf])
         torch.cuda.synchronize()
@@ -1392,7 +1497,7 @@ class GPUModel:
 
     def speculative_tokens(self, draft: "GPUModel", prompt_ids,
                            max_tokens: int, k: int = 4, eos_id=None,
-                           on_ids=None):
+                           on_ids=None, params=None):
         """Greedy decode of this engine (the target) accelerated by
         ``draft``, device-side: the token stream is this engine's own
         greedy chain under the verify pass's numerics.  Both engines are
@@ -1407,7 +1512,13 @@ class GPUModel:
         at ``max_tokens``).  Returns ``(ids, recs)``: at most ``max_tokens``
         ids, ending with the first EOS, and one ``(k, m, drafts)`` per
         verify pass that ran (the passes of a chunk that follow an EOS
-        included)."""
+        included).  ``params`` (a ``temperature`` / ``min_p``
+        ``SamplingParams`` or ``row_sampler`` dict; needs an engine built
+        with ``spec_sample=True``): stochastic speculative sampling
+        instead — the draft samples its proposals, ``spec_sample`` accepts,
+        rejects and redraws on the device, and every token is distributed
+        as this engine's own filtered distribution; the stream is a
+        function of the seed."""
         import time as _time
         if not (self.device_speculative
                 and getattr(draft, "device_speculative", False)):
@@ -1438,9 +1549,13 @@ class GPUModel:
             self._pb = draft._pb = 0
             self.prefill(prompt_ids)
             draft.prefill(prompt_ids)
-            # first token: greedy tail on the prefill logits (no length
-            # bump), handed to the draft as its pending token
-            self._sample_tail(self.b_logits, self._sv, 1, SampleSpec(),
+            # first token: greedy (sampled: the sampler row's) tail on the
+            # prefill logits (no length bump), handed to the draft as its
+            # pending token
+            sampler = None if params is None else \
+                self._spec_sampler(draft, params)
+            self._sample_tail(self.b_logits, self._sv, 1,
+                              sampler.step_spec if sampler else SampleSpec(),
                               first=True)
             draft.next_token.copy_(self.next_token)
             draft.nout.zero_()
@@ -1464,7 +1579,7 @@ class GPUModel:
                     # no more cycles than full acceptance would need: no
                     # pass ever starts past the budget, as in the host loop
                     c = min(C, -(-left // (kk + 1)), (pool - n) // (kk + 1))
-                ids, rr = self.spec_chunk(draft, kk, c, len(out))
+                ids, rr = self.spec_chunk(draft, kk, c, len(out), sampler)
                 recs.extend((kk, m, d) for m, d in rr)
                 take = [int(t) for t in ids][:left]
                 hit = [j for j, t in enumerate(take) if t in eos_set]

@@ -100,6 +100,13 @@ _SIGS = {
                                                    ctypes.c_void_p],
     "launch_spec_stage": [ctypes.c_void_p] * 3 + [ctypes.c_int,
                                                   ctypes.c_void_p],
+    "launch_spec_sample": [ctypes.c_void_p] * 2 + [ctypes.c_int] * 3 +
+                          [ctypes.c_void_p, ctypes.c_float, ctypes.c_float,
+                           ctypes.c_uint64] + [ctypes.c_void_p] * 7 +
+                          [ctypes.c_int] + [ctypes.c_void_p] * 5 +
+                          [ctypes.c_int, ctypes.c_void_p],
+    "launch_spec_keep": [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 +
+                        [ctypes.c_void_p] * 2,
     "launch_gemm_bf16": [ctypes.c_void_p] * 5 + [ctypes.c_int] * 3 +
                         [ctypes.c_void_p],
     "launch_softcap": [ctypes.c_void_p, ctypes.c_long, ctypes.c_float,
@@ -1091,6 +1098,122 @@ def spec_stage(ids: torch.Tensor, t_next: torch.Tensor,
     _spec_i32("d_ring", d_ring, max(k, 1), ids.device)
     _check(lib().launch_spec_stage(_ptr(ids), _ptr(t_next), _ptr(d_ring), k,
                                    _stream()), "spec_stage")
+
+
+# stochastic speculative sampling (csrc/spec_sample.hip SS_*): u64 scratch
+# words (2 SPEC_MAX_K + 1 row maxima, two tickets, two winners, 4 decision
+# words) and the fp32 partial masses, one per row and 2048-logit slice
+SPEC_SAMPLE_ROWS = 2 * SPEC_MAX_K + 1
+SPEC_SAMPLE_SCRATCH_WORDS = SPEC_SAMPLE_ROWS + 8
+SPEC_SAMPLE_SLICE = 2048
+
+
+def spec_sample_part_words(V: int) -> int:
+    """fp32 words of ``spec_sample``'s ``part`` for a vocabulary of V."""
+    return SPEC_SAMPLE_ROWS * (-(-int(V) // SPEC_SAMPLE_SLICE))
+
+
+def spec_sample(logits: torch.Tensor, dlogits: torch.Tensor, k: int,
+                drafts: torch.Tensor, inv_temp: float, min_p: float,
+                seed: int, ctr: torch.Tensor, scratch: torch.Tensor,
+                part: torch.Tensor, t_len: torch.Tensor,
+                t_next: torch.Tensor, t_ring: torch.Tensor,
+                t_nout: torch.Tensor, d_len: torch.Tensor,
+                d_next: torch.Tensor, d_nout: torch.Tensor,
+                rec: torch.Tensor, nrec: torch.Tensor, blocks: int = 0):
+    """Stochastic speculative verify + commit, all on the device: the
+    accept / reject rule of ``runtime.speculative.spec_accept`` under the
+    min-p filter at temperature ``1 / inv_temp`` (``min_p`` = 0: plain
+    temperature sampling).  ``logits`` (bf16 [k+1, V], contiguous) are the
+    target's rows, ``dlogits`` (fp32 [>= k, V], contiguous) the draft's rows
+    the ``k`` ``drafts`` (int32 [>= k]) were drawn from.  Draft i is accepted
+    with probability min(1, p_i(x) / q_i(x)); with m the first rejected slot
+    the token is drawn from norm(max(p_m - q_m, 0)) (from p_m where that is
+    empty), with m = k from the bonus row p_k.  The commit is
+    ``spec_verify``'s with the drawn token in the argmax's place.  The
+    uniforms and the Gumbel noise are functions of (``seed``, ``ctr``,
+    index): ``ctr`` (int64 [1]) advances by one per call and is never
+    re-armed; ``scratch`` (int64 [SPEC_SAMPLE_SCRATCH_WORDS]) and ``part``
+    (fp32 [>= spec_sample_part_words(V)]) are zeroed once by the caller and
+    re-armed by every call.  The outcome does not depend on ``blocks``
+    (blocks per row, 0 = the default).  Raises ValueError ahead of any
+    launch on a bad argument."""
+    if not isinstance(logits, torch.Tensor) \
+            or logits.dtype != torch.bfloat16:
+        raise ValueError("logits must be a bf16 tensor")
+    if not logits.is_cuda:
+        raise ValueError("spec_sample runs on the GPU; got CPU tensors")
+    if logits.dim() != 2 or not logits.is_contiguous() \
+            or logits.shape[1] < 1:
+        raise ValueError("logits must be contiguous [k+1, V >= 1]")
+    k = int(k)
+    if not 1 <= k <= SPEC_MAX_K:
+        raise ValueError(f"k must be within 1..{SPEC_MAX_K}, got {k}")
+    rows, V = logits.shape
+    if rows != k + 1:
+        raise ValueError(f"logits must have k+1 = {k + 1} rows, got {rows}")
+    dev = logits.device
+    if not isinstance(dlogits, torch.Tensor) \
+            or dlogits.dtype != torch.float32 or dlogits.dim() != 2 \
+            or not dlogits.is_contiguous() or dlogits.shape[1] != V \
+            or dlogits.shape[0] < k or dlogits.device != dev:
+        raise ValueError(f"dlogits must be contiguous fp32 [>= {k}, {V}] on "
+                         f"the logits' device")
+    inv_temp, min_p = float(inv_temp), float(min_p)
+    if not 0.0 < inv_temp < float("inf"):
+        raise ValueError(f"inv_temp must be positive, got {inv_temp}")
+    if not 0.0 <= min_p <= 1.0:
+        raise ValueError(f"min_p must be in [0, 1], got {min_p}")
+    _spec_i32("drafts", drafts, k, dev)
+    for name, t in (("t_len", t_len), ("t_next", t_next), ("t_nout", t_nout),
+                    ("d_len", d_len), ("d_next", d_next), ("d_nout", d_nout),
+                    ("nrec", nrec), ("t_ring", t_ring)):
+        _spec_i32(name, t, 1, dev)
+    if t_ring.dim() != 1:
+        raise ValueError("t_ring must be one-dimensional")
+    for name, t, n in (("scratch", scratch, SPEC_SAMPLE_SCRATCH_WORDS),
+                       ("ctr", ctr, 1)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 \
+                or not t.is_contiguous() or t.numel() < n or t.device != dev:
+            raise ValueError(f"{name} must be contiguous int64 [{n}] on the "
+                             f"logits' device")
+    need = spec_sample_part_words(V)
+    if not isinstance(part, torch.Tensor) or part.dtype != torch.float32 \
+            or not part.is_contiguous() or part.numel() < need \
+            or part.device != dev:
+        raise ValueError(f"part must be contiguous fp32 [{need}] on the "
+                         f"logits' device")
+    _spec_i32("rec", rec, SPEC_REC_WORDS, dev)
+    if rec.dim() != 2 or rec.shape[1] != SPEC_REC_WORDS:
+        raise ValueError(f"rec must be int32 [R >= 1, {SPEC_REC_WORDS}]")
+    _check(lib().launch_spec_sample(
+        _ptr(logits), _ptr(dlogits), V, k, int(blocks), _ptr(drafts),
+        ctypes.c_float(inv_temp), ctypes.c_float(min_p),
+        ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _ptr(ctr),
+        _ptr(scratch), _ptr(part), _ptr(t_len), _ptr(t_next), _ptr(t_ring),
+        _ptr(t_nout), t_ring.numel(), _ptr(d_len), _ptr(d_next),
+        _ptr(d_nout), _ptr(rec), _ptr(nrec), rec.shape[0], _stream()),
+        "spec_sample")
+
+
+def spec_keep(logits: torch.Tensor, kept: torch.Tensor, nout: torch.Tensor):
+    """``kept[nout - 1] = logits`` on the stream, ``nout`` (int32 [1]) read
+    on the device: the end of a sampled draft step keeps the row its token
+    was drawn from (fp32 [V] into fp32 [rows, V]) for ``spec_sample``.  A
+    row outside ``kept`` is dropped."""
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda:
+        raise ValueError("spec_keep runs on the GPU; got CPU tensors")
+    V = logits.numel()
+    for name, t in (("logits", logits), ("kept", kept)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 \
+                or not t.is_contiguous() or t.device != logits.device:
+            raise ValueError(f"{name} must be a contiguous fp32 tensor on "
+                             f"one device")
+    if V < 1 or kept.dim() != 2 or kept.shape[1] != V or kept.shape[0] < 1:
+        raise ValueError(f"kept must be [rows >= 1, {V}]")
+    _spec_i32("nout", nout, 1, logits.device)
+    _check(lib().launch_spec_keep(_ptr(logits), _ptr(kept), V, kept.shape[0],
+                                  _ptr(nout), _stream()), "spec_keep")
 
 
 def gemm(X: torch.Tensor, W: torch.Tensor, Y: torch.Tensor,

@@ -38,9 +38,16 @@ advertise ``device_speculative``), plain greedy params and
 (``GPUModel.speculative_tokens``): the draft replays its decode graph, the
 verify pass keeps its logits on the device and ``k_spec_verify`` commits
 the accepted prefix into both engines' state; the host reads ids and one
-small record per cycle, once per chunk of cycles.  Everything else —
-stochastic params, ``logit_bias``, TP > 1, MoE, the NumPy engine — takes
-the host loop below (``device=`` of ``generate_speculative``).
+small record per cycle, once per chunk of cycles.
+
+Device-side stochastic path: a target built with ``spec_sample=True``
+(it advertises ``device_speculative_sampling``) serves ``temperature`` and
+``min_p`` params the same way — the draft samples its proposals and keeps
+the rows it drew them from, ``spec_sample`` runs the accept / reject rule,
+the residual draw and the commit on the GPU (``spec_accept`` below is its
+specification).  Everything else — ``top_k`` / ``top_p`` / ``chain``
+params, ``logit_bias``, TP > 1, MoE, the NumPy engine — takes the host
+loop below (``device=`` of ``generate_speculative``).
 
 The reference has no speculative decoding (SURVEY §2 — single-model
 greedy/min-p only); this is a beyond-parity capability (ROADMAP §5).
@@ -124,13 +131,20 @@ def _spec_max_k() -> int:
 def device_path_block(draft, target, params: SamplingParams,
                       k: int) -> Optional[str]:
     """Why the device-side path does not apply to this call, or None when
-    it does: both engines advertise ``device_speculative``, plain greedy
-    params, no ``logit_bias``, ``k`` within ``SPEC_MAX_K``."""
+    it does: both engines advertise ``device_speculative``, greedy params
+    — or ``temperature`` / ``min_p`` params on a target that advertises
+    ``device_speculative_sampling`` —, no ``logit_bias``, ``k`` within
+    ``SPEC_MAX_K``."""
     for name, model in (("target", target), ("draft", draft)):
         if not getattr(model, "device_speculative", False):
             return f"the {name} engine has no device-side speculative path"
-    if params.strategy != "greedy":
-        return f"strategy {params.strategy!r} is not greedy"
+    if params.strategy in ("temperature", "min_p"):
+        if not getattr(target, "device_speculative_sampling", False):
+            return (f"strategy {params.strategy!r} is not greedy and the "
+                    f"target engine has no device-side speculative sampling")
+    elif params.strategy != "greedy":
+        return (f"strategy {params.strategy!r} is neither greedy nor "
+                f"temperature / min_p")
     if params.logit_bias:
         return "logit_bias is applied on the host"
     if k > _spec_max_k():
@@ -139,10 +153,11 @@ def device_path_block(draft, target, params: SamplingParams,
 
 
 def _generate_device(prompt, tokenizer, draft, target, max_tokens, k,
-                     stop_on_eos, on_token) -> GenerateResult:
-    """The device-side greedy path: ``target.speculative_tokens`` runs
-    draft steps, verify pass and commit on the GPU in chunks of cycles;
-    the host sees ids and per-cycle records only."""
+                     stop_on_eos, on_token, params) -> GenerateResult:
+    """The device-side path: ``target.speculative_tokens`` runs draft
+    steps, verify pass and commit on the GPU in chunks of cycles; the
+    host sees ids and per-cycle records only.  Stochastic ``params``
+    travel to the engine, greedy ones need none."""
     prompt_ids = [int(t) for t in tokenizer.encode(prompt)]
     eos = getattr(target.config, "eos_token_id", None)
     t0 = time.perf_counter()
@@ -150,9 +165,10 @@ def _generate_device(prompt, tokenizer, draft, target, max_tokens, k,
     if on_token is not None:
         def on_ids(new_ids):
             on_token(tokenizer.decode([int(t) for t in new_ids]))
+    kw = {} if params.strategy == "greedy" else {"params": params}
     out, recs = target.speculative_tokens(
         draft, prompt_ids, max_tokens, k=k,
-        eos_id=eos if stop_on_eos else None, on_ids=on_ids)
+        eos_id=eos if stop_on_eos else None, on_ids=on_ids, **kw)
     total = time.perf_counter() - t0
     out = [int(t) for t in out]
     t_prefill = float(getattr(target, "last_prefill_time_s", 0.0))
@@ -186,7 +202,9 @@ def generate_speculative(prompt: str, tokenizer, draft, target,
     ``device``: None routes a greedy call without ``logit_bias`` and with
     ``k <= SPEC_MAX_K`` to the device-side path when both engines
     advertise ``device_speculative`` (draft loop, verify and commit on the
-    GPU; ``on_token`` then fires once per chunk of cycles); False forces
+    GPU; ``on_token`` then fires once per chunk of cycles), and a
+    ``temperature`` / ``min_p`` call too when the target advertises
+    ``device_speculative_sampling`` (same seed, same tokens); False forces
     the host loop below; True raises ValueError where the device path does
     not apply.
     """
@@ -205,7 +223,8 @@ def generate_speculative(prompt: str, tokenizer, draft, target,
         why = device_path_block(draft, target, params, k)
         if why is None:
             return _generate_device(prompt, tokenizer, draft, target,
-                                    max_tokens, k, stop_on_eos, on_token)
+                                    max_tokens, k, stop_on_eos, on_token,
+                                    params)
         if device:
             raise ValueError(f"device-side speculative decoding does not "
                              f"apply: {why}")
